@@ -18,7 +18,19 @@ ids), 10-mer UMIs; generated on the GPU.
   scaling, value = 100M x steps / max-over-ranks time.  `--config 2` at N > 1
   gives each rank its own 100M records of disjoint cells instead (weak scaling).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5]
+A plain run does only what `value` needs: it generates the shard, warms up, times the K steps and
+prints the result line (metric, value, unit, ms_per_step, the workload, the record-count check and
+the hash of the gene rows).  `--full` adds everything measured beside it, each in runs of its own:
+the untimed per-kernel profiling pass and the roofline of the dominant kernel, the H2D / entity-count
+/ Welford drop-in side measurements, the all-reduce alone (N > 1) and the CPU baseline (N = 1).
+
+`--dump-outputs DIR` writes, after the timed steps, the rows the last timed step returned to the
+host -- cell_int, cell_float, gene_int, gene_float -- as DIR/<name>.npy in float64 (integers are
+exact there: they stay far below 2^53).  Every file holds finite numbers only: an undefined float
+metric (NaN) is written as 0 and marked in DIR/<name>_nonfinite.npy.  The shard is a function of the arguments alone, so two
+builds run with the same arguments can be compared file for file.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--full] [--dump-outputs DIR]
        (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N)
 Rank 0 prints ONE JSON line.
 """
@@ -37,7 +49,8 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 PEAK_HBM = 8.0e12  # MI355X HBM3E spec, MI355X_MICROARCH.md
-PROFILE_STEPS = 2  # untimed steps with every kernel timed (the per-kernel table)
+PROFILE_STEPS = 2  # --full: untimed steps with every kernel timed (the per-kernel table)
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all; larger arrays are sampled by rows
 
 # The unmodified reference Python gatherer timed in the build container (BASELINE.md "Measured CPU
 # reference"; it cannot run on the GPU box): context for `value`, not the cpu_baseline leg.
@@ -128,10 +141,18 @@ def parse():
     ap.add_argument("--umi-bits", type=int, default=20,
                     help="UMI ids in [0, 2^bits): 20 = 10-bp 10x v2 UMIs (default), 24 = 12-bp 10x v3")
     ap.add_argument("--float-mode", default="exact", choices=["exact", "welford"])
-    ap.add_argument("--cpu-sample-s", type=float, default=15.0, help="target seconds of CPU baseline work")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what stands beside `value`: the per-kernel profiling pass and roofline, "
+                         "the H2D / count / Welford drop-in side measurements, the all-reduce alone, the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the rows of the last timed step (cell_int, cell_float, gene_int, gene_float) "
+                         "as DIR/<name>.npy, float64; NaN entries are written as 0 and marked in "
+                         "DIR/<name>_nonfinite.npy")
+    ap.add_argument("--cpu-sample-s", type=float, default=15.0,
+                    help="--full: target seconds of CPU baseline work")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-kernel-events", action="store_true",
-                    help="time the steps without per-kernel HIP events (no roofline / kernel table)")
+                    help="--full: time the steps without HIP events on the dominant kernel (roofline.achieved is 0)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-check", action="store_true",
                     help="skip the record-count sanity checks (timing experimental engine builds only)")
@@ -146,8 +167,8 @@ def parse():
                          "bam.sort_by_tags_and_queryname (bam.py:698-709) / TagSortBam define it (default), "
                          "or CB only (all the cell and grouped gene metrics need)")
     ap.add_argument("--traffic-json", default=None,
-                    help="rocprofv3 --pmc per-kernel HBM bytes (tools/pmc_passes.sh) for roofline.traffic "
-                         "(default: the committed round-5 file of this config, profiles/r05/pmc_traffic_c<N>.json)")
+                    help="--full: rocprofv3 --pmc per-kernel HBM bytes (tools/pmc_passes.sh) for roofline.traffic "
+                         "(default: the committed round-6 file of this config, profiles/r06/pmc_traffic_c<N>.json)")
     a = ap.parse_args()
     if a.config is None:
         a.config = 2 if int(os.environ.get("WORLD_SIZE", "1")) == 1 else 3
@@ -266,22 +287,25 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    # Untimed profiling pass: HIP events around every kernel give the per-kernel table and the
-    # dominant kernel.  Bracketing every launch costs ~0.3 ms per step, so the timed steps carry
-    # events on the dominant kernel only (its average launch time is measured live there).
-    eng.profile_only("")
-    eng.profile_enable(True)
-    for _ in range(PROFILE_STEPS):
-        step()
-    torch.cuda.synchronize()
-    eng.profile_enable(False)
-    table = eng.profile_read_items()
-    dom_name = max(table.items(), key=lambda kv: kv[1][0])[0] if table else ""
+    table, dom_name = {}, ""
+    if args.full:
+        # Untimed profiling pass: HIP events around every kernel give the per-kernel table and the
+        # dominant kernel.  Bracketing every launch costs ~0.3 ms per step, so the timed steps carry
+        # events on the dominant kernel only (its average launch time is measured live there).
+        eng.profile_only("")
+        eng.profile_enable(True)
+        for _ in range(PROFILE_STEPS):
+            step()
+        torch.cuda.synchronize()
+        eng.profile_enable(False)
+        table = eng.profile_read_items()
+        dom_name = max(table.items(), key=lambda kv: kv[1][0])[0] if table else ""
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    eng.profile_only(dom_name)
-    eng.profile_enable(not args.no_kernel_events and bool(dom_name))
+    if args.full:
+        eng.profile_only(dom_name)
+        eng.profile_enable(not args.no_kernel_events and bool(dom_name))
     t0 = time.perf_counter()
     for _ in range(args.steps):
         rows = step()
@@ -289,14 +313,19 @@ def main():
     t1 = time.perf_counter()
     if world > 1:
         dist.barrier()
-    eng.profile_enable(False)
-    eng.profile_only("")
-    prof = eng.profile_read_items()
     elapsed = t1 - t0
-    allreduce_ms = time_allreduce(partials, dev) if world > 1 else None
-    step_cols = regroup(data.cols) if args.config == 5 else data.cols  # (every rank: a collective at N > 1)
-    side = side_measurements(eng, data, dims, mito, multi, args, step_cols) if rank == 0 else {}
-    del step_cols
+    if args.dump_outputs:  # (after the synchronize: the copy stream's rows of the last step are on the host)
+        dump_outputs(args.dump_outputs, world, rank, {"cell_int": host_cells[:rows], "cell_float": host_cellf[:rows],
+                                                      "gene_int": host_genei, "gene_float": host_genef})
+    prof, allreduce_ms, side = {}, None, {}
+    if args.full:
+        eng.profile_enable(False)
+        eng.profile_only("")
+        prof = eng.profile_read_items()
+        allreduce_ms = time_allreduce(partials, dev) if world > 1 else None
+        step_cols = regroup(data.cols) if args.config == 5 else data.cols  # (every rank: a collective at N > 1)
+        side = side_measurements(eng, data, dims, mito, multi, args, step_cols) if rank == 0 else {}
+        del step_cols
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -319,6 +348,66 @@ def main():
 
     total_records = job_records * args.steps
     value = total_records / elapsed
+    cpu = None
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        cpu = cpu_baseline(data, args)
+
+    if rank == 0:
+        out = {
+            "metric": "aligned records/sec for cell+gene metrics",
+            "value": value,
+            "unit": "records/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "strong" if strong else "weak",
+            "vs_baseline": None,
+            "dtype": "int64",
+            "data": "synthetic (SURVEY.md 8(d) config-%d generator, generated on GPU)" % args.config,
+            "config": {
+                "workload": ({2: "config2: %d cell-sorted records/rank",
+                              3: "config3: ONE set of %d cell-sorted records split over the ranks by cell ranges "
+                                 "balanced by records (SplitBam's invariant)",
+                              4: "config4: %d cell-sorted records/rank, lognormal(0, 2) reads per cell",
+                              5: "config5: %d globally shuffled records/rank (30%% NH>1, 40%% dup, secondary alignments), "
+                                 + ("records of every rank's cells dealt to every rank, cell bins swapped over RCCL "
+                                    "each step, then " if world > 1 else "")
+                                 + "GPU sort by " + ("(CB, UB, GE, query name)" if args.sort_order != "cell" else "CB")}
+                             [args.config]) % args.records + ", %d cells%s, %d genes; cell metrics + grouped gene metrics%s"
+                            % (args.cells, "" if strong else "/rank", args.genes, " + RCCL all-reduce" if world > 1 else ""),
+                "records_per_rank": my_records if strong else args.records,
+                "records_per_job": job_records,
+                "cells_per_rank": args.cells,
+                "genes": args.genes,
+                "float_mode": args.float_mode,
+                "umi_bits": args.umi_bits,
+                "parallelism": "cell-sharded x%d" % world + (" (rehearsal: ranks share cuda:0, gloo)" if share else ""),
+            },
+            "full": args.full,
+            # the job's gene rows (all ranks' partials summed): equal for config 2 at N = 1 and config 3
+            # at any N (exact-sum lanes), a check of the strong-scaling split
+            "gene_rows_sha256": hashlib.sha256(host_genei.numpy().tobytes() + host_genef.numpy().tobytes()).hexdigest(),
+        }
+        if args.dump_outputs:
+            out["dump_outputs"] = args.dump_outputs
+        if args.full:
+            out.update(kernel_report(args, dims, world, my_records, value, elapsed, prof, table, dom_name))
+            out.update({"cpu_baseline": cpu, "speedup_vs_cpu_baseline": (value / cpu["value"]) if cpu else None,
+                        "reference_python": REFERENCE_PYTHON, "allreduce_ms": allreduce_ms})
+        out.update(side)
+        if "h2d" in side:
+            per_step_s = elapsed / args.steps + (side["h2d"]["ms"] + side["count_entities_ms"]) / 1e3
+            out["records_per_s_incl_h2d_and_count"] = job_records / per_step_s
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def kernel_report(args, dims, world, my_records, value, elapsed, prof, table, dom_name):
+    """--full: the roofline of the dominant kernel, the sort-model yardstick and the per-kernel table,
+    from the profiling pass (`table`) and the dominant kernel's events in the timed steps (`prof`)."""
     # dominant kernel: largest total in the profiling pass; its average launch time comes from the HIP
     # events that bracketed only its launches in the timed region (on its launch stream)
     # (items: what its launches processed -- records, segment records, sort items -- as the engine
@@ -358,64 +447,38 @@ def main():
         roofline["step_traffic_frac"] = step_traffic / (elapsed / args.steps) / PEAK_HBM
     kernel_ms_per_step = {k: round(v[0] / PROFILE_STEPS, 4) for k, v in sorted(table.items(), key=lambda kv: -kv[1][0])}
     kernel_items_per_step = {k: (v[2] / PROFILE_STEPS if v[2] >= 0 else None) for k, v in table.items()}
-
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu = cpu_baseline(data, args)
-
-    if rank == 0:
-        out = {
-            "metric": "aligned records/sec for cell+gene metrics",
-            "value": value,
-            "unit": "records/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong" if strong else "weak",
-            "vs_baseline": None,
-            "dtype": "int64",
-            "data": "synthetic (SURVEY.md 8(d) config-%d generator, generated on GPU)" % args.config,
-            "config": {
-                "workload": ({2: "config2: %d cell-sorted records/rank",
-                              3: "config3: ONE set of %d cell-sorted records split over the ranks by cell ranges "
-                                 "balanced by records (SplitBam's invariant)",
-                              4: "config4: %d cell-sorted records/rank, lognormal(0, 2) reads per cell",
-                              5: "config5: %d globally shuffled records/rank (30%% NH>1, 40%% dup, secondary alignments), "
-                                 + ("records of every rank's cells dealt to every rank, cell bins swapped over RCCL "
-                                    "each step, then " if world > 1 else "")
-                                 + "GPU sort by " + ("(CB, UB, GE, query name)" if args.sort_order != "cell" else "CB")}
-                             [args.config]) % args.records + ", %d cells%s, %d genes; cell metrics + grouped gene metrics%s"
-                            % (args.cells, "" if strong else "/rank", args.genes, " + RCCL all-reduce" if world > 1 else ""),
-                "records_per_rank": my_records if strong else args.records,
-                "records_per_job": job_records,
-                "cells_per_rank": args.cells,
-                "genes": args.genes,
-                "float_mode": args.float_mode,
-                "umi_bits": args.umi_bits,
-                "parallelism": "cell-sharded x%d" % world + (" (rehearsal: ranks share cuda:0, gloo)" if share else ""),
-            },
-            "roofline": roofline,
-            "sort_model_yardstick": sort_model,
-            "kernel_ms_per_step": kernel_ms_per_step,
+    return {"roofline": roofline, "sort_model_yardstick": sort_model, "kernel_ms_per_step": kernel_ms_per_step,
             "kernel_items_per_step": kernel_items_per_step,
-            "kernel_table_source": "untimed profiling pass of %d steps (HIP events around every kernel)" % PROFILE_STEPS,
-            "cpu_baseline": cpu,
-            "speedup_vs_cpu_baseline": (value / cpu["value"]) if cpu else None,
-            "reference_python": REFERENCE_PYTHON,
-            "allreduce_ms": allreduce_ms,
-            # the job's gene rows (all ranks' partials summed): equal for config 2 at N = 1 and config 3
-            # at any N (exact-sum lanes), a check of the strong-scaling split
-            "gene_rows_sha256": hashlib.sha256(host_genei.numpy().tobytes() + host_genef.numpy().tobytes()).hexdigest(),
-        }
-        out.update(side)
-        if "h2d" in side:
-            per_step_s = elapsed / args.steps + (side["h2d"]["ms"] + side["count_entities_ms"]) / 1e3
-            out["records_per_s_incl_h2d_and_count"] = job_records / per_step_s
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+            "kernel_table_source": "untimed profiling pass of %d steps (HIP events around every kernel)" % PROFILE_STEPS}
+
+
+def dump_outputs(path, world, rank, arrays):
+    """Write the host rows of the last timed step as <path>/<name>.npy (float64; at N > 1 every rank
+    writes its cell rows as <name>.rank<r>.npy and rank 0 the all-reduced gene rows).  Arrays that
+    would take the total past DUMP_BYTES are cut to a fixed, seeded sample of their rows.
+
+    The float rows hold NaN where a metric is undefined (a gene id without records, a variance of one
+    value), as the gatherers' callers receive them.  So that every file holds finite numbers only and
+    compares with plain arithmetic, such an entry is written as 0 in <name>.npy and marked in
+    <name>_nonfinite.npy (float32, same shape: 0 finite, 1 NaN, 2 +inf, 3 -inf)."""
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_BYTES // (len(arrays) * world)
+    for name, t in arrays.items():
+        if world > 1 and name.startswith("gene") and rank != 0:
+            continue
+        a = t.numpy()
+        is_float = a.dtype.kind == "f"
+        row_bytes = (12 if is_float else 8) * max(1, a.shape[1])
+        if a.shape[0] * row_bytes > budget:
+            keep = np.random.default_rng(0).choice(a.shape[0], size=budget // row_bytes, replace=False)
+            a = a[np.sort(keep)]
+        suffix = ".rank%d" % rank if world > 1 and name.startswith("cell") else ""
+        a = a.astype(np.float64)
+        if is_float:
+            code = np.isnan(a) * 1 + np.isposinf(a) * 2 + np.isneginf(a) * 3
+            np.save(os.path.join(path, name + "_nonfinite" + suffix + ".npy"), code.astype(np.float32))
+            a = np.where(code == 0, a, 0.0)
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
 
 
 def deal_records(data, qname, n_qnames, world, rank, dev, seed):

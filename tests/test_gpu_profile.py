@@ -1,7 +1,7 @@
 """Kernel timing through the C-ABI (sct_profile_enable / sct_profile_only / sct_profile_read).
 
-bench.py's roofline depends on it: an untimed pass times every kernel (the per-kernel table and
-the dominant kernel), then the timed steps bracket only the dominant kernel's launches.
+The roofline of `bench.py --full` depends on it: an untimed pass times every kernel (the per-kernel
+table and the dominant kernel), then the timed steps bracket only the dominant kernel's launches.
 """
 import pytest
 import torch

@@ -15,6 +15,6 @@ else
 fi
 for r in a1 b1 b2 a2; do
   if [ ${r:0:1} = b ]; then E="env $ENVSW"; else E=""; fi
-  timeout -k 10 300 $E python bench.py --no-cpu-baseline "$@" > $OUT/bench_$r.json 2> $OUT/bench_$r.err || { tail -30 $OUT/bench_$r.err; exit 1; }
+  timeout -k 10 300 $E python bench.py --full --no-cpu-baseline "$@" > $OUT/bench_$r.json 2> $OUT/bench_$r.err || { tail -30 $OUT/bench_$r.err; exit 1; }
   python -c "import json; d=json.load(open('$OUT/bench_$r.json')); k=d['kernel_ms_per_step']; print('$r', 'ms/step %.3f' % d['ms_per_step'], 'welford %.1f' % d.get('dropin_cell_welford_ms', 0), {x: k[x] for x in list(k)[:8]})"
 done

@@ -7,6 +7,6 @@ OUT=gpurun_out/${1:-benches}
 mkdir -p $OUT
 for spec in "c2:" "c4:--config 4" "c5:--config 5" "v3:--umi-bits 24"; do
   name=${spec%%:*}; args=${spec#*:}
-  timeout -k 10 300 python bench.py $args > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { tail -30 $OUT/bench_$name.err; exit 1; }
+  timeout -k 10 300 python bench.py --full $args > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { tail -30 $OUT/bench_$name.err; exit 1; }
   cat $OUT/bench_$name.json
 done

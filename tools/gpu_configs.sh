@@ -5,9 +5,9 @@ set -o pipefail
 export TMPDIR=/tmp
 OUT=gpurun_out/${1:-configs}
 mkdir -p $OUT
-timeout -k 10 300 python bench.py --config 4 --no-cpu-baseline > $OUT/bench_config4.json 2> $OUT/bench_config4.err || { tail -20 $OUT/bench_config4.err; exit 1; }
+timeout -k 10 300 python bench.py --full --config 4 --no-cpu-baseline > $OUT/bench_config4.json 2> $OUT/bench_config4.err || { tail -20 $OUT/bench_config4.err; exit 1; }
 cat $OUT/bench_config4.json
-timeout -k 10 300 python bench.py --config 5 --no-cpu-baseline > $OUT/bench_config5.json 2> $OUT/bench_config5.err || { tail -20 $OUT/bench_config5.err; exit 1; }
+timeout -k 10 300 python bench.py --full --config 5 --no-cpu-baseline > $OUT/bench_config5.json 2> $OUT/bench_config5.err || { tail -20 $OUT/bench_config5.err; exit 1; }
 cat $OUT/bench_config5.json
 timeout -k 10 300 python tools/count_bench.py > $OUT/count_bench.json 2> $OUT/count_bench.err || { tail -20 $OUT/count_bench.err; exit 1; }
 cat $OUT/count_bench.json

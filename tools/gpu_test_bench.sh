@@ -13,5 +13,5 @@ if [ "$1" != "skip-tests" ]; then
 else
   shift
 fi
-timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/bench.err || { tail -30 $OUT/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/bench.err || { tail -30 $OUT/bench.err; exit 1; }
 python -c "import json; d=json.load(open('$OUT/bench.json')); print('ms/step %.3f' % d['ms_per_step'], d['kernel_ms_per_step'], d['roofline']['kernel'], round(d['roofline']['frac'],3))"
