@@ -86,22 +86,50 @@ enum : uint16_t {
   BD_MOL_MULTI = 1u << 15,
 };
 
+// flags: the BD_* split flags, and above them the key' bits the segment's records share (its depth).
+// Round 7: the depth rides with the segment because level 1 no longer cuts every entity on the same
+// number of bits (l1_width).
 struct Seg {
   uint32_t start, cnt, ent, flags;
 };
+constexpr int kSegDepthShift = 16;
+__host__ __device__ __forceinline__ int seg_depth(uint32_t flags) { return (int)(flags >> kSegDepthShift); }
+// digit bits of the level below a segment of `depth` fixed bits
+__host__ __device__ __forceinline__ int level_bits(int KB, int depth) {
+  return KB - depth < kRadixBits ? KB - depth : kRadixBits;
+}
+
+// Level-1 digit width of an entity (a level-0 segment) of `size` records (round 7): as many top bits
+// of k1' as leave children of about kL1Target records -- a 10k-record cell is cut 32 ways, not 256,
+// so a key-pass batch leaves runs of ~32 records per child instead of ~4, and the plan reserves and
+// the classification describes 8 times fewer children.  The mean child stays well under kBCap, so
+// ordinary children stay terminal buckets.  `force` (SCT_L1_BITS, a test switch): a uniform width.
+// One rule for k_level1_plan, the level-1 k_bucket_classify and k_build_keys_run.
+#ifndef SCT_L1_TARGET
+#define SCT_L1_TARGET 384
+#endif
+constexpr int kL1Target = SCT_L1_TARGET;
+constexpr int kL1MinBits = 3;
+static_assert(3 * kL1Target < 2 * kBCap, "the mean level-1 child stays well under a terminal bucket's capacity");
+__host__ __device__ __forceinline__ int l1_width(uint32_t size, int force) {
+  if (force) return force;
+  const uint32_t q = (size + kL1Target - 1) / kL1Target;  // children of kL1Target records
+  const int w = q <= 1 ? 0 : 32 - __builtin_clz(q - 1);   // ceil(log2(q))
+  return w < kL1MinBits ? kL1MinBits : (w > kRadixBits ? kRadixBits : w);
+}
 struct alignas(16) Pay {
   uint64_t w0, w1;
 };
 __device__ __forceinline__ uint64_t pay_w0(const Pay* p, size_t i) {  // w0 alone: an 8-byte load
   return reinterpret_cast<const uint64_t*>(p)[2 * i];
 }
-struct alignas(16) Work {  // one chunk of a segment: its records [beg, beg + n), n <= kChunk
-  uint32_t seg, beg, n, pad;
+struct alignas(16) Work {  // one chunk of a segment: its records [beg, beg + n), n <= kChunk,
+  uint32_t seg, beg, n, depth;  // and the segment's depth (no dependent segment load in hist / scatter)
 };
-__device__ __forceinline__ Work make_work(uint32_t id, uint32_t start, uint32_t cnt, uint32_t k) {
-  const uint32_t b = start + k * (uint32_t)kChunk;
-  const uint32_t r = start + cnt - b;
-  return Work{id, b, r < (uint32_t)kChunk ? r : (uint32_t)kChunk, 0u};
+__device__ __forceinline__ Work make_work(uint32_t id, const Seg& sg, uint32_t k) {
+  const uint32_t b = sg.start + k * (uint32_t)kChunk;
+  const uint32_t r = sg.start + sg.cnt - b;
+  return Work{id, b, r < (uint32_t)kChunk ? r : (uint32_t)kChunk, (uint32_t)seg_depth(sg.flags)};
 }
 // Device counters of one level (n_giant and n_big accumulate over levels).  Round 5: no record
 // counters (n_rec, n_big_rec) -- every classify block with a pushed or big child added to them, and
@@ -129,7 +157,7 @@ __device__ __forceinline__ void push_segment(const Seg& sg, Seg* __restrict__ se
   seg[id] = sg;
   const uint32_t nw = (sg.cnt + kChunk - 1) / kChunk;
   const uint32_t w0 = atomicAdd(&ctr[1], nw);
-  for (uint32_t k = 0; k < nw; k++) work[w0 + k] = make_work(id, sg.start, sg.cnt, k);
+  for (uint32_t k = 0; k < nw; k++) work[w0 + k] = make_work(id, sg, k);
 }
 
 // level 0: small entities are terminal buckets, mid-sized ones big buckets; larger ones segments,
@@ -156,7 +184,7 @@ __global__ void k_bucket_level0(const int64_t* __restrict__ ent_start, int64_t n
 }
 
 __global__ void __launch_bounds__(kBlock) k_bucket_hist(const Pay* __restrict__ pin, const Seg* __restrict__ seg,
-                                                        const Work* __restrict__ work, int shift, int bits,
+                                                        const Work* __restrict__ work, int KB,
                                                         uint32_t* __restrict__ hist) {
   __shared__ uint32_t h[kWaves][kRadix];
   const int wid = threadIdx.x / kWave;
@@ -164,6 +192,8 @@ __global__ void __launch_bounds__(kBlock) k_bucket_hist(const Pay* __restrict__ 
   const Work wk = work[xcd_tile(blockIdx.x, gridDim.x)];  // the chunk's range rides in the work item:
   const uint32_t beg = wk.beg;                             // no dependent segment load before the keys
   const uint32_t end = wk.beg + wk.n;
+  const int bits = level_bits(KB, (int)wk.depth);  // the segment's digit: the next bits below its depth
+  const int shift = KB - (int)wk.depth - bits + kKeyShift;
   const uint64_t mask = (1ull << bits) - 1;
   __syncthreads();
   for (uint32_t p = beg + threadIdx.x; p < end; p += kBlock) atomicAdd(&h[wid][(pay_w0(pin, p) >> shift) & mask], 1u);
@@ -226,7 +256,7 @@ constexpr int kSItems = kChunk / kSBlock;
 static_assert(kRadix <= kSBlock, "one thread per digit");
 __global__ void __launch_bounds__(kSBlock) k_bucket_scatter(const Pay* __restrict__ pin, Pay* __restrict__ pout,
                                                             const Seg* __restrict__ seg, const Work* __restrict__ work,
-                                                            int shift, int bits, uint32_t* __restrict__ cur) {
+                                                            int KB, uint32_t* __restrict__ cur) {
   __shared__ Pay s_pay[kChunk];
   __shared__ uint32_t s_cnt[kRadix];
   __shared__ uint32_t s_start[kRadix];
@@ -236,6 +266,8 @@ __global__ void __launch_bounds__(kSBlock) k_bucket_scatter(const Pay* __restric
   const Work wk = work[xcd_tile(blockIdx.x, gridDim.x)];
   const uint32_t beg = wk.beg;
   const int tile_n = (int)wk.n;
+  const int bits = level_bits(KB, (int)wk.depth);
+  const int shift = KB - (int)wk.depth - bits + kKeyShift;
   const uint32_t mask = (1u << bits) - 1;
   if (t < kRadix) s_cnt[t] = 0;
   __syncthreads();
@@ -310,11 +342,13 @@ __device__ __forceinline__ uint32_t split_flags(int Kb, int depth, int depth1, i
 // with one atomic each.
 // by_ent (level 1 planned before the key pass, segment.h k_level1_plan): the counts are per entity,
 // hist[entity][digit], and each is replaced by its child's start | kL1SegMark for the key pass;
-// the grid is an upper bound and *n_seg_dev the number of segments.
+// the grid is an upper bound and *n_seg_dev the number of segments; the digit is l1_width(records,
+// l1_force) bits wide (digits past it hold no records).  Otherwise the segment's digit is the next
+// level_bits below its depth.  A pushed child carries its depth in its flags.
 constexpr uint32_t kL1SegMark = 0x80000000u;
 __global__ void __launch_bounds__(kBlock) k_bucket_classify(const Seg* __restrict__ seg,
                                                             uint32_t* __restrict__ hist,
-                                                            uint32_t* __restrict__ cur, int depth, int bits,
+                                                            uint32_t* __restrict__ cur, int l1_force,
                                                             int K1, int KM, int KB, int parity, int by_ent,
                                                             uint16_t* __restrict__ bdesc, uint32_t* __restrict__ bent,
                                                             Seg* __restrict__ nseg, Work* __restrict__ nwork,
@@ -334,7 +368,8 @@ __global__ void __launch_bounds__(kBlock) k_bucket_classify(const Seg* __restric
   const uint32_t start = sg.start + (uint32_t)block_exclusive_scan<uint64_t>((uint64_t)c, &tot_c, s_scan);
   cur[i] = start;
   if (by_ent) hist[hi] = start | kL1SegMark;
-  const int depth1 = depth + bits;
+  const int depth = seg_depth(sg.flags);  // (0 at level 1)
+  const int depth1 = depth + (by_ent ? l1_width(sg.cnt, l1_force) : level_bits(KB, depth));
   uint32_t fl = 0;
   if (c) {
     fl = split_flags(K1, depth, depth1, d, sg.flags, s_c, BD_K1_NOHEAD, BD_K1_MULTI);
@@ -367,8 +402,9 @@ __global__ void __launch_bounds__(kBlock) k_bucket_classify(const Seg* __restric
   __syncthreads();
   if (push) {
     const uint32_t id = s_base[0] + so;
-    nseg[id] = Seg{start, c, sg.ent, fl};
-    for (uint32_t k = 0; k < nw; k++) nwork[s_base[1] + wo + k] = make_work(id, start, c, k);
+    const Seg child{start, c, sg.ent, fl | ((uint32_t)depth1 << kSegDepthShift)};
+    nseg[id] = child;
+    for (uint32_t k = 0; k < nw; k++) nwork[s_base[1] + wo + k] = make_work(id, child, k);
   }
 }
 

@@ -51,7 +51,7 @@ constexpr int64_t kEntHistMax = 1 << 18;  // entities whose first partition leve
 struct Layout {
   size_t tile_cnt, scalars, scan_sums, pay_a, pay_b, half, counts, offsets, ent_start, partials;
   size_t gcounts, gcursor, gtoff, gwork, dflags, gpay, seen, zero_mito, ent_hist, l1_toff, l1_tslot;
-  size_t bdesc, bent, seg_a, seg_b, work_a, work_b, seg_hist, seg_cur, giants, bigs, wctl, worder, wx, total;
+  size_t head_bits, bdesc, bent, seg_a, seg_b, work_a, work_b, seg_hist, seg_cur, giants, bigs, wctl, worder, wx, total;
   int64_t num_tiles, num_chunks, max_ent, max_gene_work, max_seg, max_work, count_cap;
   int n_buckets;
   bool gene;
@@ -87,6 +87,7 @@ Layout layout_for(const sct_plan_t* plan) {
   L.counts = take(sizeof(uint32_t) * (size_t)m);
   L.offsets = take(sizeof(uint32_t) * (size_t)m);
   L.ent_start = take(sizeof(int64_t) * (size_t)(L.max_ent + 1));
+  L.head_bits = take(sizeof(uint64_t) * (size_t)cdiv(n1, 64));  // one bit per record: run heads (k_heads)
   L.partials = take(sizeof(int64_t) * SCT_NP * (size_t)L.max_ent);
   L.gcounts = take(L.gene ? sizeof(uint32_t) * (size_t)L.n_buckets : 0);  // records per gene bucket
   L.gcursor = take(L.gene ? sizeof(uint32_t) * (size_t)L.n_buckets : 0);
@@ -164,11 +165,14 @@ int check_plan(const sct_plan_t* plan, const sct_records_t* rec) {
 // heads + scan of the entity column; with `dup_check`, also flags cell ids seen in two runs.
 // Copies (n_entities, dup flag) to the host and synchronizes.
 // pre: a fill queued behind the count's copy (round 6: it runs while the host waits for the count)
+// publish (the pipeline: the workspace is a whole one, not sct_count_entities' prefix; round 7): the
+// head bitmap and, queued behind the scan, the entity starts, also written while the host waits
 int count_runs(const int32_t* ent, int64_t n, void* ws, const Layout& L, bool dup_check, int32_t n_ids,
-               int64_t* n_ent, bool* dup, hipStream_t s, FillBatch* pre = nullptr) {
+               int64_t* n_ent, bool* dup, hipStream_t s, FillBatch* pre = nullptr, bool publish = false) {
   const int64_t tiles = cdiv(n, kTile);
   uint64_t* tc = at<uint64_t>(ws, L.tile_cnt);
   uint64_t* sc = at<uint64_t>(ws, L.scalars);
+  uint64_t* hb = publish ? at<uint64_t>(ws, L.head_bits) : nullptr;
   uint32_t* seen = nullptr;
   FillBatch fb;
   if (dup_check) {
@@ -178,11 +182,15 @@ int count_runs(const int32_t* ent, int64_t n, void* ws, const Layout& L, bool du
   fb.add(sc, 2 * sizeof(uint64_t));
   if (int rc = launch_fills(fb, s)) return rc;
   if (((uintptr_t)ent & 15) == 0) {
-    LAUNCH_N("heads", n, k_heads4, dim3((unsigned)tiles), dim3(kBlock), s, ent, n, tc, seen, (uint32_t)n_ids, sc + 1);
+    LAUNCH_N("heads", n, k_heads4, dim3((unsigned)tiles), dim3(kBlock), s, ent, n, tc, seen, (uint32_t)n_ids, sc + 1, hb);
   } else {
-    LAUNCH_N("heads", n, k_heads, dim3((unsigned)tiles), dim3(kBlock), s, ent, n, tc, seen, (uint32_t)n_ids, sc + 1);
+    LAUNCH_N("heads", n, k_heads, dim3((unsigned)tiles), dim3(kBlock), s, ent, n, tc, seen, (uint32_t)n_ids, sc + 1, hb);
   }
   LAUNCH("scan", k_scan_wide, dim3(1), dim3(kScanWide), s, tc, tiles, sc);
+  if (publish) {
+    LAUNCH("ent_starts", k_ent_starts, dim3((unsigned)cdiv(tiles, kWaves)), dim3(kBlock), s, (const uint64_t*)hb,
+           (const uint64_t*)tc, (const uint64_t*)sc, n, L.max_ent, at<int64_t>(ws, L.ent_start));
+  }
   uint64_t host[2] = {0, 0};
   if (pre) {
     if (int rb = readback_start(sc, sizeof(host), s)) return rb;
@@ -227,20 +235,21 @@ void level1_fills(const Layout& L, void* ws, int64_t n, int64_t n_ent, const L1P
 }
 
 int bucket_level1_plan(const Layout& L, void* ws, const KeyCols& kc, int64_t n, int64_t n_ent, const Bits& b,
-                       int64_t* ent_start, const L1Plan& l1, hipStream_t s) {
+                       const int64_t* ent_start, const L1Plan& l1, hipStream_t s) {
   uint16_t* bdesc = at<uint16_t>(ws, L.bdesc);
   uint32_t* bent = at<uint32_t>(ws, L.bent);
   BucketCtl* ctl = bucket_ctl(ws, L);
   uint32_t* ctr0 = level0_ctr(ws, L);
   const int KB = b.k1 + b.k2 + b.h;
-  LAUNCH_N("level1_plan", n, k_level1_plan, dim3((unsigned)cdiv(n, kKTile)), dim3(kBlock), s, kc.ent, kc.k1, kc.n_k1, n,
-         (const uint64_t*)at<uint64_t>(ws, L.tile_cnt), b, b.k1 - kRadixBits, ent_start, l1);
+  LAUNCH_N("level1_plan", n, k_level1_plan, dim3((unsigned)cdiv(n, kKTile)), dim3(kBlock), s,
+           (const uint64_t*)at<uint64_t>(ws, L.head_bits), kc.k1, kc.n_k1, n,
+           (const uint64_t*)at<uint64_t>(ws, L.tile_cnt), b, ent_start, l1);
   LAUNCH("bucket_level0", k_bucket_level0, dim3((unsigned)cdiv(n_ent, kBlock)), dim3(kBlock), s, ent_start, n_ent, n,
          bdesc, bent, at<Seg>(ws, L.seg_a), at<Work>(ws, L.work_a), at<Seg>(ws, L.bigs), ctl, ctr0);
   const int64_t max_seg = n_ent < n / (kBigCap + 1) + 1 ? n_ent : n / (kBigCap + 1) + 1;
   if (max_seg > L.max_seg) return fail(SCT_ENOMEM, "level 1: %lld segments exceed the workspace", (long long)max_seg);
   LAUNCH("bucket_classify", k_bucket_classify, dim3((unsigned)max_seg), dim3(kBlock), s,
-         (const Seg*)at<Seg>(ws, L.seg_a), l1.hist, at<uint32_t>(ws, L.seg_cur), 0, kRadixBits, b.k1, b.k1 + b.k2, KB,
+         (const Seg*)at<Seg>(ws, L.seg_a), l1.hist, at<uint32_t>(ws, L.seg_cur), l1.bits, b.k1, b.k1 + b.k2, KB,
          1, 1, bdesc, bent, at<Seg>(ws, L.seg_b), at<Work>(ws, L.work_b), at<Seg>(ws, L.giants), at<Seg>(ws, L.bigs),
          ctl, (const uint32_t*)ctr0);
   return SCT_OK;
@@ -326,9 +335,8 @@ int bucket_distinct(const Layout& L, void* ws, int64_t n, int64_t n_ent, const i
   BucketCtl* ctl = bucket_ctl(ws, L);
   const int KB = b.k1 + b.k2 + b.h;
   Seg* bigs = at<Seg>(ws, L.bigs);
-  int depth = 0, level = 1, c = 0;
+  int level = 1, c = 0;  // (each segment carries its own depth: bucket.h Seg)
   if (planned) {
-    depth = KB < kRadixBits ? KB : kRadixBits;
     level = 2;
     c = 1;
   } else {
@@ -390,23 +398,21 @@ int bucket_distinct(const Layout& L, void* ws, int64_t n, int64_t n_ent, const i
     if ((int64_t)h.n_seg > L.max_seg || (int64_t)h.n_work > L.max_work)
       return fail(SCT_ENOMEM, "bucket level %d: %u segments / %u work items exceed the workspace", level, h.n_seg,
                   h.n_work);
-    const int bits = KB - depth < kRadixBits ? KB - depth : kRadixBits;
-    const int shift = KB - depth - bits + kKeyShift;
     const int src = (level - 1) & 1;
     const Pay* pin = src ? pb : pa;
     Pay* pout = src ? pa : pb;
     HIPCHK(hipMemsetAsync(hist, 0, sizeof(uint32_t) * kRadix * (size_t)h.n_seg, s));
     LAUNCH("bucket_hist", k_bucket_hist, dim3(h.n_work), dim3(kBlock), s, pin, (const Seg*)seg[c],
-           (const Work*)work[c], shift, bits, hist);
+           (const Work*)work[c], KB, hist);
     HIPCHK(hipMemsetAsync(ctl, 0, 2 * sizeof(uint32_t), s));  // next level's n_seg, n_work
-    LAUNCH("bucket_classify", k_bucket_classify, dim3(h.n_seg), dim3(kBlock), s, (const Seg*)seg[c], hist, cur, depth,
-           bits, b.k1, b.k1 + b.k2, KB, level & 1, 0, bdesc, bent, seg[c ^ 1], work[c ^ 1], giants, bigs, ctl,
+    LAUNCH("bucket_classify", k_bucket_classify, dim3(h.n_seg), dim3(kBlock), s, (const Seg*)seg[c], hist, cur, 0,
+           b.k1, b.k1 + b.k2, KB, level & 1, 0, bdesc, bent, seg[c ^ 1], work[c ^ 1], giants, bigs, ctl,
            (const uint32_t*)nullptr);
     // the next level's counts are final after classify: read them while the scatter runs
     if (int rb = readback_start(ctl, sizeof(h), s)) return rb;
     const uint32_t n_work = h.n_work;
     LAUNCH("bucket_scatter", k_bucket_scatter, dim3(n_work), dim3(kSBlock), s, pin, pout,
-           (const Seg*)seg[c], (const Work*)work[c], shift, bits, cur);
+           (const Seg*)seg[c], (const Work*)work[c], KB, cur);
     if (int rb = readback_finish(&h, sizeof(h))) return rb;
     if (err_pending) {
       err_pending = false;
@@ -419,7 +425,6 @@ int bucket_distinct(const Layout& L, void* ws, int64_t n, int64_t n_ent, const i
       big_done = h.n_big;
     }
     c ^= 1;
-    depth += bits;
     level++;
   }
   const dim3 tgrid((unsigned)cdiv(n, kWin));
@@ -465,18 +470,19 @@ int bucket_distinct(const Layout& L, void* ws, int64_t n, int64_t n_ent, const i
 template <bool kBucket, bool kStreams>
 int launch_build_keys(bool cell, bool gene, dim3 grid, hipStream_t s, const KeyCols& kc, const RecCols& rc2,
                       const uint8_t* mito, int64_t n, const uint64_t* toff, const Bits& b, uint64_t* keys,
-                      void* vals, int64_t* ent_start, int64_t* partials, uint32_t* gcounts, int n_buckets,
+                      void* vals, const uint64_t* head_bits, const int64_t* ent_start, int64_t* partials,
+                      uint32_t* gcounts, int n_buckets,
                       uint32_t* err, uint32_t* gwide, uint32_t* gtoff, const L1Plan& l1) {
   if (cell && gene) {
     LAUNCH_SHM_N("build_keys", n, (k_build_keys_run<true, true, kBucket, kStreams>), grid, dim3(kBlock),
-               sizeof(uint32_t) * (size_t)n_buckets, s, kc, rc2, mito, n, toff, b, keys, vals, ent_start, partials,
+               sizeof(uint32_t) * (size_t)n_buckets, s, kc, rc2, mito, n, toff, b, keys, vals, head_bits, ent_start, partials,
                gcounts, n_buckets, err, gwide, gtoff, l1);
   } else if (cell) {
     LAUNCH_N("build_keys", n, (k_build_keys_run<true, false, kBucket, kStreams>), grid, dim3(kBlock), s, kc, rc2, mito, n,
-           toff, b, keys, vals, ent_start, partials, gcounts, n_buckets, err, gwide, gtoff, l1);
+           toff, b, keys, vals, head_bits, ent_start, partials, gcounts, n_buckets, err, gwide, gtoff, l1);
   } else {
     LAUNCH_N("build_keys", n, (k_build_keys_run<false, false, kBucket, kStreams>), grid, dim3(kBlock), s, kc, rc2, mito,
-           n, toff, b, keys, vals, ent_start, partials, gcounts, n_buckets, err, gwide, gtoff, l1);
+           n, toff, b, keys, vals, head_bits, ent_start, partials, gcounts, n_buckets, err, gwide, gtoff, l1);
   }
   return SCT_OK;
 }
@@ -661,7 +667,7 @@ int pipeline(const sct_plan_t* plan, const sct_records_t* rec, const uint8_t* ge
                         !(nol1 && nol1[0] == '1') && !(nopre && nopre[0] == '1') && n > 0;
   FillBatch pre;
   if (may_plan) pre.add(at<uint16_t>(ws, L.bdesc), sizeof(uint16_t) * (size_t)n);
-  int rc = count_runs(ent_col, n, ws, L, gene, plan->n_cell_ids, &n_ent, &dup, s, may_plan ? &pre : nullptr);
+  int rc = count_runs(ent_col, n, ws, L, gene, plan->n_cell_ids, &n_ent, &dup, s, may_plan ? &pre : nullptr, true);
   if (rc) return rc;
   if (dup) return fail(SCT_EINVAL, "grouped gene partials need cell-sorted records (a cell id forms two runs)");
   if (n_ent > L.max_ent)
@@ -697,14 +703,16 @@ int pipeline(const sct_plan_t* plan, const sct_records_t* rec, const uint8_t* ge
     b.inv = inv & b.k1_mask();
   }
 
-  KeyCols kc{ent_col, cell ? rec->gene : rec->cell, rec->umi, (uint32_t)(cell ? plan->n_gene_ids : plan->n_cell_ids),
+  KeyCols kc{cell ? rec->gene : rec->cell, rec->umi, (uint32_t)(cell ? plan->n_gene_ids : plan->n_cell_ids),
              (uint32_t)plan->n_umi_ids};
   RecCols rc2{rec->ref, rec->pos, rec->gq_sum, rec->gq_len, rec->gq_gt30, rec->bits, rec->xf,
               rec->cy_gt30, rec->cy_len, rec->uy_gt30, rec->uy_len};
   SortBuffers B{at<uint64_t>(ws, L.pay_a), at<uint64_t>(ws, L.pay_b), at<uint32_t>(ws, L.pay_a + L.half),
                 at<uint32_t>(ws, L.pay_b + L.half), at<uint32_t>(ws, L.counts), at<uint32_t>(ws, L.offsets),
                 at<uint64_t>(ws, L.scan_sums), L.count_cap};
-  int64_t* ent_start = at<int64_t>(ws, L.ent_start);
+  // run heads (one bit per record) and entity starts (+ the sentinel ent_start[n_ent] = n): count_runs
+  const uint64_t* hbits = at<uint64_t>(ws, L.head_bits);
+  const int64_t* ent_start = at<int64_t>(ws, L.ent_start);
   int64_t* partials = at<int64_t>(ws, L.partials);
   uint32_t* gcounts = gene ? at<uint32_t>(ws, L.gcounts) : nullptr;
   uint32_t* gtoff = gene ? at<uint32_t>(ws, L.gtoff) : nullptr;
@@ -713,9 +721,14 @@ int pipeline(const sct_plan_t* plan, const sct_records_t* rec, const uint8_t* ge
   const bool planned = bucket && L.max_ent <= kEntHistMax && n_ent > 0 && b.k1 >= kRadixBits &&
                        !(nol1 && nol1[0] == '1');
   L1Plan l1{};
-  if (planned)
+  if (planned) {
+    // SCT_L1_BITS=1..8 (a test switch): every entity's first level on that many bits (8: the uniform
+    // cut of the rounds before 7) instead of the width its size asks for (bucket.h l1_width)
+    const char* l1b = getenv("SCT_L1_BITS");
+    const int forced = l1b ? atoi(l1b) : 0;
     l1 = L1Plan{at<uint32_t>(ws, L.ent_hist), at<uint32_t>(ws, L.l1_toff), at<uint2>(ws, L.l1_tslot),
-                at<Pay>(ws, L.pay_b)};
+                at<Pay>(ws, L.pay_b), forced >= 1 && forced <= kRadixBits ? forced : 0};
+  }
   const uint8_t* mito = gene_is_mito;
   // every buffer the step zeroes before its first kernel, in one launch
   FillBatch fb;
@@ -763,15 +776,15 @@ int pipeline(const sct_plan_t* plan, const sct_records_t* rec, const uint8_t* ge
 
   if (bucket) {
     uint64_t* pay = at<uint64_t>(ws, L.pay_a);  // (the bucket path writes Pay records through `keys`)
-    rc = streams ? launch_build_keys<true, true>(cell, gene, tgrid, s, kc, rc2, mito, n, toff, b, pay, nullptr, ent_start,
-                                                 partials, gcounts, L.n_buckets, &ctl->err, gwide, gtoff, l1)
-                 : launch_build_keys<true, false>(cell, gene, tgrid, s, kc, rc2, mito, n, toff, b, pay, nullptr, ent_start,
-                                                  partials, gcounts, L.n_buckets, &ctl->err, gwide, gtoff, l1);
+    rc = streams ? launch_build_keys<true, true>(cell, gene, tgrid, s, kc, rc2, mito, n, toff, b, pay, nullptr, hbits,
+                                                 ent_start, partials, gcounts, L.n_buckets, &ctl->err, gwide, gtoff, l1)
+                 : launch_build_keys<true, false>(cell, gene, tgrid, s, kc, rc2, mito, n, toff, b, pay, nullptr, hbits,
+                                                  ent_start, partials, gcounts, L.n_buckets, &ctl->err, gwide, gtoff, l1);
   } else {
-    rc = streams ? launch_build_keys<false, true>(cell, gene, tgrid, s, kc, rc2, mito, n, toff, b, B.ka, B.va,
+    rc = streams ? launch_build_keys<false, true>(cell, gene, tgrid, s, kc, rc2, mito, n, toff, b, B.ka, B.va, hbits,
                                                   ent_start, partials, gcounts, L.n_buckets, &ctl->err, gwide, gtoff,
                                                   l1)
-                 : launch_build_keys<false, false>(cell, gene, tgrid, s, kc, rc2, mito, n, toff, b, B.ka, B.va,
+                 : launch_build_keys<false, false>(cell, gene, tgrid, s, kc, rc2, mito, n, toff, b, B.ka, B.va, hbits,
                                                    ent_start, partials, gcounts, L.n_buckets, &ctl->err, gwide, gtoff,
                                                    l1);
     if (rc) return rc;
@@ -780,7 +793,7 @@ int pipeline(const sct_plan_t* plan, const sct_records_t* rec, const uint8_t* ge
     if (err & 2) return fail(SCT_EINVAL, "a gene / cell / umi id lies outside its dictionary size");
   }
   if (rc) return rc;
-  if (!wf_fork_early && !exact && out_i) {  // the entity starts exist now (the key pass wrote them)
+  if (!wf_fork_early && !exact && out_i) {
     rc = welford_stage(L, ws, cell, n, n_ent, rc2, ent_start, out_f, s, wf);
     if (rc) return rc;
   }

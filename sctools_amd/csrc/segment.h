@@ -1,9 +1,9 @@
 // segment.h -- the input-order pass: entity runs (bam.iter_tag_groups, bam.py:492-540),
 // packed sort keys, and every per-record additive metric of the entity.
 //
-// One block owns a tile of kTile consecutive records.  The entity column is staged
-// into LDS with coalesced loads, run heads are found on blocked items, and a block
-// scan numbers the runs.  Then each thread walks the tile in striped order (all
+// One block owns a tile of kTile consecutive records.  Run heads are found once per step
+// (k_heads4 / k_heads) and published as one bit per record; the plan and the key pass load
+// their tile's bits and a block scan numbers the runs.  Then each thread walks the tile in striped order (all
 // column loads coalesced), builds the key [run | k1 | k2 | fragment hash] and the
 // value (record index, bit 31 = unmapped), and sums the metrics that are plain
 // per-record sums in the reference (aggregator.py:259-334, 507-530) into the run's
@@ -23,22 +23,30 @@ namespace sct {
 // heads per tile.  With `seen` set (grouped gene partials), every run head also bumps
 // seen[entity value]; a value seen twice means the column is not sorted into single
 // runs and *dup_flag gets bit 0; a value outside [0, n_ids) sets bit 1.
+// With `head_bits` set (the pipeline; sct_count_entities' workspace prefix has no room for them), the
+// heads are also published as one bit per record position, cdiv(n, 64) words in positional order:
+// the words tile_run_ids keeps in s_hb, so that the plan and the key pass need not read the column again.
 __global__ void k_heads(const int32_t* __restrict__ key, int64_t n, uint64_t* __restrict__ tile_cnt,
-                        uint32_t* __restrict__ seen, uint32_t n_ids, uint64_t* __restrict__ dup_flag) {
+                        uint32_t* __restrict__ seen, uint32_t n_ids, uint64_t* __restrict__ dup_flag,
+                        uint64_t* __restrict__ head_bits) {
   const int64_t base = (int64_t)blockIdx.x * kTile;
   uint64_t c = 0;
 #pragma unroll 4
   for (int j = 0; j < kItems; j++) {
+    const int64_t p0 = base + (int64_t)j * kBlock + (threadIdx.x & ~(kWave - 1));  // the wave's first position
     const int64_t p = base + (int64_t)j * kBlock + threadIdx.x;
+    bool h = false;
     if (p < n) {
       const int32_t v = key[p];
-      const bool h = (p == 0 || v != key[p - 1]);
+      h = (p == 0 || v != key[p - 1]);
       c += h ? 1 : 0;
       if (h && seen) {
         if ((uint32_t)v >= n_ids) atomicOr((unsigned long long*)dup_flag, 2ull);  // id outside the dictionary
         else if (atomicAdd(&seen[v], 1u) != 0u) atomicOr((unsigned long long*)dup_flag, 1ull);
       }
     }
+    const uint64_t m = __ballot(h);
+    if (head_bits && (threadIdx.x & (kWave - 1)) == 0 && p0 < n) head_bits[p0 >> 6] = m;
   }
   __shared__ uint64_t red[kWaves];
   c = wave_sum(c);
@@ -56,8 +64,12 @@ __global__ void k_heads(const int32_t* __restrict__ key, int64_t n, uint64_t* __
 // 16-byte aligned column (the host checks and falls back to k_heads).
 __global__ void __launch_bounds__(kBlock) k_heads4(const int32_t* __restrict__ key, int64_t n,
                                                    uint64_t* __restrict__ tile_cnt, uint32_t* __restrict__ seen,
-                                                   uint32_t n_ids, uint64_t* __restrict__ dup_flag) {
+                                                   uint32_t n_ids, uint64_t* __restrict__ dup_flag,
+                                                   uint64_t* __restrict__ head_bits) {
   constexpr int kVec = kItems / 4;
+  // head_bits: a thread's four head bits are a nibble of the tile's bitmap; two lanes make a byte
+  __shared__ uint64_t s_bits[kTile / 64];
+  static_assert(kTile / 64 <= kBlock, "one thread per bitmap word");
   const int64_t base = (int64_t)blockIdx.x * kTile;
   const int lane = threadIdx.x & (kWave - 1);
   int4 v[kVec];
@@ -80,16 +92,21 @@ __global__ void __launch_bounds__(kBlock) k_heads4(const int32_t* __restrict__ k
     int32_t prev = __shfl_up(v[j].w, 1);
     if (lane == 0 && p > 0 && p < n) prev = key[p - 1];
     const int32_t r[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+    uint32_t nib = 0;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
       const bool in = p + i < n;
       const bool h = in && (p + i == 0 || r[i] != (i == 0 ? prev : r[i - 1]));
       c += h ? 1 : 0;
+      nib |= (h ? 1u : 0u) << i;
       if (h && seen) {
         if ((uint32_t)r[i] >= n_ids) atomicOr((unsigned long long*)dup_flag, 2ull);  // id outside the dictionary
         else if (atomicAdd(&seen[r[i]], 1u) != 0u) atomicOr((unsigned long long*)dup_flag, 1ull);
       }
     }
+    const uint32_t hi = (uint32_t)__shfl_down((int)nib, 1);
+    if (head_bits && !(lane & 1))  // tile positions 8 ((j kBlock + t) / 2) + [0, 8)
+      reinterpret_cast<uint8_t*>(s_bits)[(j * kBlock + (int)threadIdx.x) >> 1] = (uint8_t)(nib | (hi << 4));
   }
   __shared__ uint64_t red[kWaves];
   c = wave_sum(c);
@@ -100,10 +117,36 @@ __global__ void __launch_bounds__(kBlock) k_heads4(const int32_t* __restrict__ k
     for (int w = 0; w < kWaves; w++) t += red[w];
     tile_cnt[blockIdx.x] = t;
   }
+  if (head_bits && threadIdx.x < kTile / 64 && base + 64 * (int64_t)threadIdx.x < n)
+    head_bits[(base >> 6) + threadIdx.x] = s_bits[threadIdx.x];
 }
 
-struct KeyCols {
-  const int32_t* ent;  // column whose runs are the entities
+// Entity starts from the published head bits and the scanned tile counts: ent_start[r] = the position
+// of head r, and the sentinel ent_start[n_ent] = n.  One wave per kTile tile, one bitmap word per lane.
+// Queued before the host knows the entity count: `cap` (the plan's entity bound) guards every store.
+__global__ void __launch_bounds__(kBlock) k_ent_starts(const uint64_t* __restrict__ head_bits,
+                                                       const uint64_t* __restrict__ tile_off,
+                                                       const uint64_t* __restrict__ n_ent, int64_t n, int64_t cap,
+                                                       int64_t* __restrict__ ent_start) {
+  static_assert(kTile / 64 == kWave, "one bitmap word per lane");
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t tile = (int64_t)blockIdx.x * kWaves + threadIdx.x / kWave;
+  const int64_t p0 = tile * kTile + 64 * (int64_t)lane;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && (int64_t)*n_ent <= cap) ent_start[*n_ent] = n;
+  if (tile * kTile >= n) return;  // wave-uniform
+  uint64_t m = p0 < n ? head_bits[p0 >> 6] : 0ull;
+  const uint32_t cnt = (uint32_t)__popcll(m);
+  uint32_t inc = cnt;  // inclusive wave scan
+  for (int off = 1; off < kWave; off <<= 1) {
+    const uint32_t y = (uint32_t)__shfl_up((int)inc, off);
+    if (lane >= off) inc += y;
+  }
+  int64_t r = (int64_t)tile_off[tile] + (inc - cnt);
+  for (; m; m &= m - 1, r++)
+    if (r <= cap) ent_start[r] = p0 + (__ffsll((unsigned long long)m) - 1);
+}
+
+struct KeyCols {  // (the entity column itself is read by k_heads alone: its runs travel as head bits)
   const int32_t* k1;
   const int32_t* k2;
   uint32_t n_k1, n_k2;  // dictionary sizes: ids outside them set bit 1 of *err
@@ -145,37 +188,18 @@ static_assert(kKTile <= 65535, "local run ids are 16-bit");
 
 // Number the runs of the tile.  Run ids are local: the run of tile position q is the returned base
 // (tile_off - 1) plus the number of heads at positions <= q (local 0 = the run continuing from the
-// previous tile).  Heads are found on striped, coalesced loads (the previous record comes from the
-// neighbouring lane; lane 0 re-reads it, a cache hit) and kept as one bit per position (s_hb:
-// kKTile / 64 words, ballots); a block scan counts each thread's 32 blocked positions' heads, and
-// s_wpre gets the heads before each 64-position word, so loc_of() reads any position's run id off
-// two LDS words.  Writes ent_start[run] for heads when ent_start is set.  Block-wide (barriers).
+// previous tile).  The heads come from the bitmap k_heads / k_heads4 published (one bit per position,
+// zero past n; round 7: the column itself is not read again) into s_hb (kKTile / 64 words); a block
+// scan counts each thread's 32 blocked positions' heads, and s_wpre gets the heads before each
+// 64-position word, so loc_of() reads any position's run id off two LDS words.  Block-wide (barriers).
 // Also returns the thread's blocked head mask (*my_heads) and the local id of the run before its
 // first position (*my_ex): the run of position 32t + j is ebase + my_ex + popc(heads & bits 0..j).
-__device__ __forceinline__ int64_t tile_run_ids(const int32_t* __restrict__ ent, int64_t base, int tile_n,
+__device__ __forceinline__ int64_t tile_run_ids(const uint64_t* __restrict__ head_bits, int64_t base, int64_t n,
                                                 uint64_t tile_off, uint64_t* s_hb, uint64_t* s_scan,
-                                                int64_t* __restrict__ ent_start, uint32_t* my_heads,
-                                                uint32_t* my_ex, uint32_t* n_heads, uint16_t* s_wpre) {
-  const int t = threadIdx.x, lane = t & (kWave - 1), w = t / kWave;
-  for (int j0 = 0; j0 < kKItems; j0 += kRunBatch) {
-    int32_t v[kRunBatch], pv[kRunBatch];
-#pragma unroll
-    for (int u = 0; u < kRunBatch; u++) {
-      const int q = (j0 + u) * kBlock + t;
-      const int64_t p = base + (q < tile_n ? q : 0);
-      v[u] = ent[p];
-      pv[u] = (lane == 0 && p > 0) ? ent[p - 1] : 0;
-    }
-#pragma unroll
-    for (int u = 0; u < kRunBatch; u++) {
-      const int q = (j0 + u) * kBlock + t;
-      const int32_t up = __shfl_up(v[u], 1);
-      const int32_t prev = lane == 0 ? pv[u] : up;
-      const bool h = q < tile_n && (base + q == 0 || v[u] != prev);
-      const uint64_t m = __ballot(h);
-      if (lane == 0) s_hb[(j0 + u) * kWaves + w] = m;  // positions 64 ((j0 + u) kWaves + w) + [0, 64)
-    }
-  }
+                                                uint32_t* my_heads, uint32_t* my_ex, uint32_t* n_heads,
+                                                uint16_t* s_wpre) {
+  const int t = threadIdx.x;
+  if (t < kKTile / 64) s_hb[t] = base + 64 * (int64_t)t < n ? head_bits[(base >> 6) + t] : 0ull;
   __syncthreads();
   const uint32_t heads = reinterpret_cast<const uint32_t*>(s_hb)[t];  // blocked positions 32t .. 32t+31
   uint64_t tot;
@@ -185,13 +209,6 @@ __device__ __forceinline__ int64_t tile_run_ids(const int32_t* __restrict__ ent,
   *my_ex = (uint32_t)ex;
   *n_heads = (uint32_t)tot;  // the tile's last run has local id n_heads
   if (!(t & 1)) s_wpre[t >> 1] = (uint16_t)ex;  // thread 2i starts word i (kKItems == 32)
-  if (ent_start) {
-    const int q0 = t * kKItems;
-    for (uint32_t hb = heads; hb; hb &= hb - 1) {
-      const int j = __ffs(hb) - 1;
-      ent_start[ebase + (uint32_t)ex + (uint32_t)__popc(heads & ((2u << j) - 1u))] = base + q0 + j;
-    }
-  }
   __syncthreads();
   return ebase;
 }
@@ -210,15 +227,17 @@ __device__ __forceinline__ uint32_t loc_of(int q, const uint64_t* s_hb, const ui
 // every payload of a segment straight into its level-1 child instead of writing it in input order
 // for k_bucket_scatter to move once more (aggregator.py:264, 300-303: the molecule and fragment
 // Counters this grouping serves):
-//   k_level1_plan      per key-pass tile: run ids (ent_start), each record's level-1 digit counted
+//   k_level1_plan      per key-pass tile: run ids, each record's level-1 digit counted
 //                      per (entity, digit) in l1.hist (the children's sizes), and the tile's range
 //                      inside every child it feeds, reserved with one atomic per (slot, digit): l1.toff;
 //   k_bucket_classify  (level 1) turns l1.hist into the children's starts, in place, marked kL1Seg;
 //   k_build_keys_run   ranks each segment record inside its tile's range with one LDS atomic.
 // Only runs that can be segments get a slot: the tile's first and last runs and the runs of more
 // than kBigCap records inside it (at most two: a tile holds kKTile < 3 (kBigCap + 1) records).
-// The digit is the top kRadixBits of key' = [k1' | k2 | hash]; the host takes this path when they
-// come from k1' alone (k1 >= kRadixBits bits): digit = k1' >> (k1 - kRadixBits).
+// The digit is the top w <= kRadixBits bits of key' = [k1' | k2 | hash], w by the entity's size
+// (bucket.h l1_width; round 7); the host takes this path when they come from k1' alone (k1 >=
+// kRadixBits bits): digit = k1' >> (k1 - w).  l1.hist and l1.toff keep kRadix entries per entity and
+// slot: digits >= 2^w stay zero.
 constexpr int kL1Slots = 4;
 constexpr uint32_t kL1NoSlot = 0xffffu;
 constexpr uint32_t kL1Seg = kL1SegMark;  // l1.hist entry of a classified segment: child start | kL1Seg
@@ -228,7 +247,12 @@ struct L1Plan {
   uint32_t* toff;  // [tile][kL1Slots][kRadix]: the tile's offset inside each child it feeds
   uint2* tslot;    // [tile]: the slots' local run ids, 16 bits each (kL1NoSlot: none)
   Pay* pay_b;      // the level-1 children's buffer (B)
+  int bits;        // 0: each entity's digit width by its size (bucket.h l1_width); else that width for all
 };
+// the level-1 digit width of run e, from the entity starts (ent_start[n_ent] = n: k_ent_starts)
+__device__ __forceinline__ int l1_run_width(const int64_t* __restrict__ ent_start, int64_t e, int force) {
+  return l1_width((uint32_t)(ent_start[e + 1] - ent_start[e]), force);
+}
 __device__ __forceinline__ uint32_t l1_slot_loc(uint2 ts, int k) {
   return ((k < 2 ? ts.x : ts.y) >> (16 * (k & 1))) & 0xffffu;
 }
@@ -241,10 +265,10 @@ __device__ __forceinline__ int slot_of(uint32_t loc, const uint32_t (&sl)[kN]) {
   return r;
 }
 
-__global__ void __launch_bounds__(kBlock) k_level1_plan(const int32_t* __restrict__ ent, const int32_t* __restrict__ k1col,
-                                                        uint32_t n_k1, int64_t n, const uint64_t* __restrict__ tile_off,
-                                                        Bits b, int dshift, int64_t* __restrict__ ent_start,
-                                                        L1Plan l1) {
+__global__ void __launch_bounds__(kBlock) k_level1_plan(const uint64_t* __restrict__ head_bits,
+                                                        const int32_t* __restrict__ k1col, uint32_t n_k1, int64_t n,
+                                                        const uint64_t* __restrict__ tile_off, Bits b,
+                                                        const int64_t* __restrict__ ent_start, L1Plan l1) {
   __shared__ uint64_t s_scan[kWaves + 1];
   __shared__ uint64_t s_hb[kKTile / 64];
   __shared__ uint16_t s_wpre[kKTile / 64];
@@ -259,8 +283,8 @@ __global__ void __launch_bounds__(kBlock) k_level1_plan(const int32_t* __restric
   if (t < kL1Slots) s_slot[t] = kL1NoSlot;
   if (t == 0) s_nmid = 0;
   uint32_t heads, ex, n_heads;  // (tile_run_ids' barriers publish the initialisation above)
-  const int64_t ebase = tile_run_ids(ent, base, tile_n, tile_off[(size_t)blockIdx.x * kKTilesPerBlock], s_hb,
-                                     s_scan, ent_start, &heads, &ex, &n_heads, s_wpre);
+  const int64_t ebase = tile_run_ids(head_bits, base, n, tile_off[(size_t)blockIdx.x * kKTilesPerBlock], s_hb,
+                                     s_scan, &heads, &ex, &n_heads, s_wpre);
   const uint32_t first = loc_of(0, s_hb, s_wpre);  // the run at the tile's first position
   // inner runs with more than kBigCap records in the tile: head h and position h + kBigCap in one run
   for (uint32_t hb = heads; hb; hb &= hb - 1) {
@@ -277,9 +301,24 @@ __global__ void __launch_bounds__(kBlock) k_level1_plan(const int32_t* __restric
     if (n_heads != first) s_slot[kL1Slots - 1] = n_heads;
   }
   __syncthreads();
+  // Each slot's digit: the top w = l1_width bits of k1', by its run's size (block-uniform loads, in
+  // flight with the first batch's column loads).  A narrow digit would pile a wave's 64 records onto
+  // 2^w counters, so the slot's kRadix counters hold kRadix >> w copies of them, picked by the lane:
+  // counter (lane copy << w) | digit; the copies are summed at the end.
   uint32_t sl[kL1Slots];
+  int wd[kL1Slots];
 #pragma unroll
-  for (int k = 0; k < kL1Slots; k++) sl[k] = s_slot[k];
+  for (int k = 0; k < kL1Slots; k++) {
+    sl[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_slot[k]);
+    wd[k] = sl[k] != kL1NoSlot ? l1_run_width(ent_start, ebase + sl[k], l1.bits) : kRadixBits;
+  }
+  const auto pick = [&wd](int k) {
+    int r = wd[0];
+#pragma unroll
+    for (int i = 1; i < kL1Slots; i++) r = k == i ? wd[i] : r;
+    return r;
+  };
+  const uint32_t lane = (uint32_t)t & (kWave - 1);
   for (int j0 = 0; j0 < kKItems; j0 += kRunBatch) {  // striped, loads of kRunBatch rounds in flight
     uint32_t v[kRunBatch];
 #pragma unroll
@@ -299,10 +338,12 @@ __global__ void __launch_bounds__(kBlock) k_level1_plan(const int32_t* __restric
     }
     if (ku >= 0) {
       uint32_t* h = &s_h[ku * kRadix];
+      const int w = pick(ku), dshift = b.k1 - w;
+      const uint32_t copy = (lane & ((kRadix >> w) - 1u)) << w;
 #pragma unroll
       for (int u = 0; u < kRunBatch; u++) {
         const uint32_t k1 = v[u] < n_k1 ? v[u] : 0u;  // the key pass's rule for an invalid id
-        atomicAdd(&h[b.scramble(k1) >> dshift], 1u);
+        atomicAdd(&h[copy | (b.scramble(k1) >> dshift)], 1u);
       }
     } else if (ku == -2) {
 #pragma unroll
@@ -311,14 +352,18 @@ __global__ void __launch_bounds__(kBlock) k_level1_plan(const int32_t* __restric
         if (q >= tile_n) continue;
         const uint32_t k1 = v[u] < n_k1 ? v[u] : 0u;
         const int k = slot_of(loc_of(q, s_hb, s_wpre), sl);
-        if (k >= 0) atomicAdd(&s_h[k * kRadix + (b.scramble(k1) >> dshift)], 1u);
+        if (k < 0) continue;
+        const int w = pick(k);
+        atomicAdd(&s_h[k * kRadix + (((lane & ((kRadix >> w) - 1u)) << w) | (b.scramble(k1) >> (b.k1 - w)))], 1u);
       }
     }
   }
   __syncthreads();
 #pragma unroll
   for (int k = 0; k < kL1Slots; k++) {
-    const uint32_t c = s_h[k * kRadix + t];
+    uint32_t c = 0;  // digit t of slot k: its copies' sum
+    if (t < (1 << wd[k]))
+      for (int r = 0; r < (kRadix >> wd[k]); r++) c += s_h[k * kRadix + (r << wd[k]) + t];
     if (sl[k] != kL1NoSlot && c)
       l1.toff[((size_t)blockIdx.x * kL1Slots + k) * kRadix + t] =
           atomicAdd(&l1.hist[(size_t)(ebase + sl[k]) * kRadix + t], c);
@@ -510,7 +555,8 @@ template <bool kCell, bool kGene, bool kBucket, bool kStreams>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))) k_build_keys_run(KeyCols c, RecCols r, const uint8_t* __restrict__ k1_is_mito,
                                                            int64_t n, const uint64_t* __restrict__ tile_off, Bits b,
                                                            uint64_t* __restrict__ keys, void* __restrict__ vals,
-                                                           int64_t* __restrict__ ent_start,
+                                                           const uint64_t* __restrict__ head_bits,
+                                                           const int64_t* __restrict__ ent_start,
                                                            int64_t* __restrict__ partials,
                                                            uint32_t* __restrict__ gene_counts, int n_buckets,
                                                            uint32_t* __restrict__ err, uint32_t* __restrict__ gwide,
@@ -543,10 +589,10 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))
   __shared__ Pay s_stage[kL1 ? kStage : 1];
   __shared__ uint32_t s_bc[kL1 ? 2 * kRadix : 1];
   __shared__ uint32_t s_gd[kL1 ? 2 * kRadix : 1];
+  // s_lsh: key' >> s_lsh[slot] is the level-1 digit of the slot's run, l1_width bits by its size
+  // (the plan's and the classification's rule; key' < 2^KB, so the digit needs no mask)
+  __shared__ int s_lsh[kL1Slots];
   const int KB = b.k1 + b.k2 + b.h;
-  const int bits1 = KB < kRadixBits ? KB : kRadixBits;
-  const int sh1 = KB - bits1;
-  const uint32_t dmask = (1u << bits1) - 1u;
   const uint64_t tile_off0 = tile_off[(size_t)blockIdx.x * kKTilesPerBlock];
   const bool planned = kBucket && l1.hist != nullptr;  // uniform
   if constexpr (kBucket) {
@@ -562,7 +608,10 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))
           seg = (v & kL1Seg) != 0;  // every digit of a classified segment carries the mark
           if (seg) s_pos[k * kRadix + t] = (v & ~kL1Seg) + l1.toff[((size_t)blockIdx.x * kL1Slots + k) * kRadix + t];
         }
-        if (t == 0) s_lslot[k] = seg ? l : kL1NoSlot;
+        if (t == 0) {
+          s_lslot[k] = seg ? l : kL1NoSlot;
+          s_lsh[k] = seg ? KB - l1_run_width(ent_start, (int64_t)tile_off0 - 1 + l, l1.bits) : 0;
+        }
       }
       s_bc[t] = 0;
       s_bc[kRadix + t] = 0;
@@ -570,8 +619,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))
   }
   // 1-2. run index of every record of the tile
   uint32_t my_heads, my_ex, n_heads;
-  const int64_t ebase = tile_run_ids(c.ent, base, tile_n, tile_off0, s_hb, s_scan, planned ? nullptr : ent_start,
-                                     &my_heads, &my_ex, &n_heads, s_wpre);
+  const int64_t ebase = tile_run_ids(head_bits, base, n, tile_off0, s_hb, s_scan, &my_heads, &my_ex, &n_heads, s_wpre);
   uint32_t lsl[kL1Slots];
 #pragma unroll
   for (int k = 0; k < kL1Slots; k++) lsl[k] = planned ? s_lslot[k] : kL1NoSlot;
@@ -627,6 +675,9 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))
       bs1 = bhi != blo ? slot_of(bhi, lsl) : -1;
     }
     const bool stage = bs0 >= 0 || bs1 >= 0;
+    // the two batch slots' digit shifts (block-uniform)
+    const int dsh0 = bs0 >= 0 ? __builtin_amdgcn_readfirstlane(s_lsh[bs0]) : 0;
+    const int dsh1 = bs1 >= 0 ? __builtin_amdgcn_readfirstlane(s_lsh[bs1]) : 0;
     uint32_t rk[kKeyBatch];  // staged records: batch slot << 16 | rank in (slot, digit); else kDirect
     uint32_t t0 = 0, n_staged = 0;
     if constexpr (kBucket) {
@@ -640,7 +691,8 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))
           const int ls = (loc == blo && bs0 >= 0) ? 0 : (loc == bhi && bs1 >= 0) ? 1 : -1;
           if (ls < 0) continue;
           const uint32_t k1 = (uint32_t)vk1[u] < c.n_k1 ? (uint32_t)vk1[u] : 0u;  // (the rule below)
-          const uint32_t dg = (uint32_t)(((uint64_t)b.scramble(k1) << (b.k2 + b.h)) >> sh1) & dmask;
+          const uint32_t dg =
+              (uint32_t)(((uint64_t)b.scramble(k1) << (b.k2 + b.h)) >> (ls ? dsh1 : dsh0)) & (kRadix - 1);
           rk[u] = ((uint32_t)ls << 16) | atomicAdd(&s_bc[ls * kRadix + dg], 1u);
         }
         __syncthreads();
@@ -704,7 +756,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))
         const Pay x{payload_w0(kp, ref, rev, mapped, mito), ((uint64_t)p << 32) | (uint32_t)pos};
         if (stage && rk[u] != kDirect) {
           const uint32_t ls = rk[u] >> 16;
-          const uint32_t dg = (uint32_t)(kp >> sh1) & dmask;
+          const uint32_t dg = (uint32_t)(kp >> (ls ? dsh1 : dsh0)) & (kRadix - 1);
           s_stage[s_bc[ls * kRadix + dg] + (rk[u] & 0xffffu)] = x;
         } else {
           reinterpret_cast<Pay*>(keys)[p] = x;  // (the bucket path's keys are payload buffer A)
@@ -743,7 +795,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))
         s_bc[kRadix + t] = 0;
         for (uint32_t q = t; q < n_staged; q += kBlock) {
           const Pay x = s_stage[q];
-          const uint32_t dg = (uint32_t)(x.w0 >> (sh1 + kKeyShift)) & dmask;
+          const uint32_t dg = (uint32_t)(x.w0 >> ((q >= t0 ? dsh1 : dsh0) + kKeyShift)) & (kRadix - 1);
           l1.pay_b[s_gd[(q >= t0 ? kRadix : 0) + dg] + q] = x;
         }
         __syncthreads();
