@@ -8,10 +8,11 @@ HDRS := $(wildcard sctools_amd/csrc/*.h) include/sctools_gpu.h
 BAMDEC := sctools_amd/libsct_bam.so
 CSVFMT := sctools_amd/libsct_csv.so
 GBAM := sctools_amd/libsct_gbam.so
+BARCODE := sctools_amd/libsct_barcode.so
 
 SI4 := tests/native/libsct_engine_si4.so
 
-all: $(ENGINE) $(BAMDEC) $(CSVFMT) $(GBAM) oracle/liboracle.so tests/native/libfxcheck.so $(SI4)
+all: $(ENGINE) $(BAMDEC) $(CSVFMT) $(GBAM) $(BARCODE) oracle/liboracle.so tests/native/libfxcheck.so $(SI4)
 
 $(ENGINE): $(SRC) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -o $@ $(SRC) -L/opt/rocm/lib -lrccl
@@ -20,11 +21,14 @@ $(ENGINE): $(SRC) $(HDRS)
 $(SI4): $(SRC) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -DSCT_SORT_ITEMS=4 -o $@ $(SRC) -L/opt/rocm/lib -lrccl
 
-$(BAMDEC): sctools_amd/csrc/bamdec.cpp sctools_amd/csrc/bamsplit.cpp sctools_amd/csrc/bgzf.h include/sct_bam.h
-	g++ -O3 -std=c++17 -fopenmp -fPIC -shared -Wall -o $@ sctools_amd/csrc/bamdec.cpp sctools_amd/csrc/bamsplit.cpp -lz
+$(BAMDEC): sctools_amd/csrc/bamdec.cpp sctools_amd/csrc/bamsplit.cpp sctools_amd/csrc/bamtag.cpp sctools_amd/csrc/bamwrite.h sctools_amd/csrc/bgzf.h include/sct_bam.h
+	g++ -O3 -std=c++17 -fopenmp -fPIC -shared -Wall -o $@ sctools_amd/csrc/bamdec.cpp sctools_amd/csrc/bamsplit.cpp sctools_amd/csrc/bamtag.cpp -lz
 
 $(GBAM): sctools_amd/csrc/gbam.hip sctools_amd/csrc/inflate.h sctools_amd/csrc/bgzf.h include/sct_gbam.h include/sct_bam.h
 	$(HIPCC) $(HIPFLAGS) -o $@ sctools_amd/csrc/gbam.hip -lz
+
+$(BARCODE): sctools_amd/csrc/barcode.hip include/sct_barcode.h
+	$(HIPCC) $(HIPFLAGS) -o $@ sctools_amd/csrc/barcode.hip
 
 $(CSVFMT): sctools_amd/csrc/csvfmt.cpp include/sct_csv.h
 	g++ -O3 -std=c++17 -fopenmp -fPIC -shared -Wall -o $@ sctools_amd/csrc/csvfmt.cpp -lz
@@ -36,6 +40,6 @@ tests/native/libfxcheck.so: tests/native/fxcheck.cpp sctools_amd/csrc/fixedpt.h
 	g++ -O2 -std=c++17 -ffp-contract=off -fPIC -shared -o $@ tests/native/fxcheck.cpp
 
 clean:
-	rm -f $(ENGINE) $(BAMDEC) $(CSVFMT) $(GBAM) oracle/liboracle.so tests/native/libfxcheck.so $(SI4)
+	rm -f $(ENGINE) $(BAMDEC) $(CSVFMT) $(GBAM) $(BARCODE) oracle/liboracle.so tests/native/libfxcheck.so $(SI4)
 
 .PHONY: all clean

@@ -108,6 +108,41 @@ int sct_bam_split(const char* const* in_paths, int32_t n_in, const char* out_pre
 int sct_bam_write_order(const char* in_path, const char* out_path, const int64_t* perm, int64_t n, int32_t level,
                         int32_t n_threads);
 
+/* ErrorsToCorrectBarcodesMap.correct_bam's host side (barcode.py:357-379: pysam get_tag("CR") per
+ * record, set_tag("CB"), write): one string tag of every record as a fixed-length column, and the
+ * file written back with another tag set from such a column.
+ *
+ * sct_bam_tag_collect inflates `in_path` and keeps its records until sct_bam_tag_close.  For every
+ * record it finds the first `src_tag` (two characters, e.g. "CR") and the first `dst_tag` ("CB")
+ * the record may already carry.  A record without `src_tag` is SCT_BAM_KEYERROR (the reference's
+ * second get_tag raises it), a non-string value SCT_BAM_ETYPED; the first such record in file
+ * order decides and *bad_record (if set) is its index.  Nothing has been written by then. */
+typedef struct sct_bam_tags sct_bam_tags_t;
+int sct_bam_tag_collect(const char* in_path, const char* src_tag, const char* dst_tag, int32_t L, int32_t n_threads,
+                        sct_bam_tags_t** out, int64_t* bad_record);
+
+/* Number of records. */
+int64_t sct_bam_tag_n(const sct_bam_tags_t* t);
+
+/* n x L bytes, row-major: record i's source value where it has exactly L bytes, zeros elsewhere. */
+const uint8_t* sct_bam_tag_values(const sct_bam_tags_t* t);
+
+/* The records whose source value has another length: *n of them, their indices (ascending) and
+ * their values, entry k = bytes[offsets[k] .. offsets[k + 1]). */
+int sct_bam_tag_others(const sct_bam_tags_t* t, int64_t* n, const int64_t** records, const char** bytes,
+                       const int64_t** offsets);
+
+/* Writes every collected record to `out_path` under the input's header with `dst_tag`:Z set: the
+ * first `dst_tag` the record carried is removed and the new one appended as the last tag (what
+ * pysam's set_tag does); every other byte of the record is unchanged.  Record i's value is row i
+ * of `values` (n x L) where its source value has L bytes; for the k-th other record it is
+ * other_bytes[other_offsets[k] .. other_offsets[k + 1]), or, with those NULL, its own source
+ * value (correct_bam's `except KeyError` pass-through).  BGZF output as sct_bam_write_order's. */
+int sct_bam_tag_write(const sct_bam_tags_t* t, const char* out_path, const char* dst_tag, const uint8_t* values,
+                      const char* other_bytes, const int64_t* other_offsets, int32_t level, int32_t n_threads);
+
+void sct_bam_tag_close(sct_bam_tags_t* t);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,7 +29,8 @@ class TypedTagValue(Exception):
 CELL_METRICS, GENE_METRICS, COUNT_MATRIX, SORT_KEYS = 0, 1, 2, 3
 _MODES = {"cell": CELL_METRICS, "gene": GENE_METRICS, "count": COUNT_MATRIX, "sortkeys": SORT_KEYS}
 EXPORTED = ("sct_bam_decode", "sct_bam_decode_tags", "sct_bam_last_error", "sct_bam_n", "sct_bam_column", "sct_bam_dictionary",
-            "sct_bam_close", "sct_bam_split", "sct_bam_write_order")
+            "sct_bam_close", "sct_bam_split", "sct_bam_write_order", "sct_bam_tag_collect", "sct_bam_tag_n",
+            "sct_bam_tag_values", "sct_bam_tag_others", "sct_bam_tag_write", "sct_bam_tag_close")
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -65,6 +66,20 @@ def load() -> ctypes.CDLL:
                                 i32, i32, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_int64)]
     L.sct_bam_write_order.restype = ctypes.c_int
     L.sct_bam_write_order.argtypes = [ctypes.c_char_p, ctypes.c_char_p, vp, ctypes.c_int64, i32, i32]
+    L.sct_bam_tag_collect.restype = ctypes.c_int
+    L.sct_bam_tag_collect.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, i32, i32, ctypes.POINTER(vp),
+                                      ctypes.POINTER(ctypes.c_int64)]
+    L.sct_bam_tag_n.restype = ctypes.c_int64
+    L.sct_bam_tag_n.argtypes = [vp]
+    L.sct_bam_tag_values.restype = vp
+    L.sct_bam_tag_values.argtypes = [vp]
+    L.sct_bam_tag_others.restype = ctypes.c_int
+    L.sct_bam_tag_others.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                     ctypes.POINTER(vp)]
+    L.sct_bam_tag_write.restype = ctypes.c_int
+    L.sct_bam_tag_write.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, vp, ctypes.c_char_p, vp, i32, i32]
+    L.sct_bam_tag_close.restype = None
+    L.sct_bam_tag_close.argtypes = [vp]
     _lib = L
     return L
 
@@ -154,3 +169,67 @@ def write_order(in_path: str, out_path: str, perm, level: int = 6, threads: int 
                                int(p.size), int(level), int(threads))
     if rc != OK:
         raise _EXC.get(rc, RuntimeError)(L.sct_bam_last_error().decode("utf-8", "replace"))
+
+
+class TagColumn:
+    """sct_bam_tag_*: the string tag ``src_tag`` of every record of ``path`` as an ``[n, length]`` byte
+    column, and the file written back with ``dst_tag`` set from such a column.  A context manager:
+    the inflated records are held until it exits."""
+
+    def __init__(self, path: str, src_tag: str, dst_tag: str, length: int, threads: int = 0):
+        self._lib = load()
+        self._h = ctypes.c_void_p()
+        self.length = int(length)
+        self.dst_tag = dst_tag
+        bad = ctypes.c_int64(-1)
+        rc = self._lib.sct_bam_tag_collect(os.fsencode(path), src_tag.encode(), dst_tag.encode(), self.length,
+                                           int(threads), ctypes.byref(self._h), ctypes.byref(bad))
+        if rc != OK:
+            raise _EXC.get(rc, RuntimeError)(self._lib.sct_bam_last_error().decode("utf-8", "replace"))
+        self.n = int(self._lib.sct_bam_tag_n(self._h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.sct_bam_tag_close(self._h)
+            self._h = ctypes.c_void_p()
+
+    def _bytes(self, ptr, count: int) -> np.ndarray:
+        if not count:
+            return np.zeros(0, dtype=np.uint8)
+        return np.frombuffer((ctypes.c_char * count).from_address(ptr), dtype=np.uint8, count=count).copy()
+
+    def values(self) -> np.ndarray:
+        """uint8 [n, length]: the values of exactly ``length`` bytes, zeros for the others."""
+        return self._bytes(self._lib.sct_bam_tag_values(self._h), self.n * self.length).reshape(self.n, self.length)
+
+    def others(self):
+        """The values of another length, in record order."""
+        cnt, rec, by, off = ctypes.c_int64(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        self._lib.sct_bam_tag_others(self._h, ctypes.byref(cnt), ctypes.byref(rec), ctypes.byref(by), ctypes.byref(off))
+        k = int(cnt.value)
+        offs = np.frombuffer((ctypes.c_int64 * (k + 1)).from_address(off.value), dtype=np.int64)
+        raw = ctypes.string_at(by.value, int(offs[-1])) if int(offs[-1]) else b""
+        return [raw[offs[i]:offs[i + 1]].decode("utf-8") for i in range(k)]
+
+    def write(self, out_path: str, values: np.ndarray, others=None, level: int = 6, threads: int = 0) -> None:
+        """The records to ``out_path`` with ``dst_tag`` set: row i of ``values`` where the record's
+        source value fits, else the matching entry of ``others`` (None: its own source value)."""
+        v = np.ascontiguousarray(values, dtype=np.uint8)
+        if v.shape != (self.n, self.length):
+            raise ValueError("values must be [%d, %d], got %s" % (self.n, self.length, v.shape))
+        ob, oo = None, None
+        if others is not None:
+            enc = [s.encode("utf-8") for s in others]
+            ob = b"".join(enc)
+            oo = np.concatenate([[0], np.cumsum([len(e) for e in enc], dtype=np.int64)]).astype(np.int64)
+        rc = self._lib.sct_bam_tag_write(self._h, os.fsencode(out_path), self.dst_tag.encode(),
+                                         v.ctypes.data if v.size else None, ob,
+                                         oo.ctypes.data if oo is not None else None, int(level), int(threads))
+        if rc != OK:
+            raise _EXC.get(rc, RuntimeError)(self._lib.sct_bam_last_error().decode("utf-8", "replace"))

@@ -1,0 +1,463 @@
+"""
+Nucleotide barcode sets and whitelist error correction -- the reference's ``sctools.barcode``
+(``barcode.py``) with the same class names and signatures, the work on the GPU
+(``libsct_barcode.so``, ``include/sct_barcode.h``).
+
+``Barcodes``                    a set of 2-bit encoded barcodes: base frequencies and diversity on
+                                the host, the all-pairs Hamming summary on the GPU.
+``ErrorsToCorrectBarcodesMap``  corrects a barcode within Hamming distance 1 of a whitelist.
+
+The reference builds a dict of every single-base error of every whitelist barcode
+(``barcode.py:311-335``, 1 + 4*L keys per barcode) and looks each record up in it.  The dict is
+filled in file order and later writers overwrite earlier ones, so what it computes is
+
+    corrected(x) = the whitelist barcode with the largest file index among those at Hamming
+                   distance <= 1 from x, or KeyError if there is none,
+
+where a query byte outside ``ACGT`` can match only if it is the single such byte and is ``N``.
+Here the whitelist is a host index (barcode -> largest file index) for single lookups and a hash
+table in device memory for arrays and BAM files; no error dict is ever built.
+
+Whitelist lines that the table cannot hold -- another length than the first line's, or a character
+outside ``ACGT`` (the reference's bundled ``1k-august-2016.txt`` ends with such a line) -- are kept in
+a small host map built by the reference's rule, and an answer is the larger file index of the two.
+"""
+import ctypes
+import os
+from collections import Counter
+from typing import Iterable, Iterator, Mapping, Optional
+
+import numpy as np
+
+from sctools_amd import consts
+from sctools_amd.encodings import TwoBit
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(HERE, "libsct_barcode.so")
+
+MAX_CORRECT_LENGTH = 31  # a 62-bit code leaves a value free for the table's empty slot
+MAX_PAIR_LENGTH = 32
+MAX_PAIR_BARCODES = 1 << 22
+HIST_BINS = 33
+
+EXPORTED = ("sct_bc_last_error", "sct_bc_table_size", "sct_bc_table_build", "sct_bc_correct", "sct_bc_pair_hist")
+
+_lib: Optional[ctypes.CDLL] = None
+
+
+class BarcodeError(RuntimeError):
+    """A libsct_barcode.so call returned an error code (message from sct_bc_last_error)."""
+
+
+def load() -> ctypes.CDLL:
+    """Load the HIP barcode library; raise loudly if it was not built."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise ImportError("sctools_amd barcode library not built (%s missing); run `python -c "
+                          "'import __graft_entry__ as g; g.build()'`" % LIB_PATH)
+    L = ctypes.CDLL(LIB_PATH)
+    vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
+    L.sct_bc_last_error.restype = ctypes.c_char_p
+    L.sct_bc_last_error.argtypes = []
+    L.sct_bc_table_size.restype = ctypes.c_int
+    L.sct_bc_table_size.argtypes = [i64, ctypes.POINTER(ctypes.c_size_t)]
+    L.sct_bc_table_build.restype = ctypes.c_int
+    L.sct_bc_table_build.argtypes = [vp, i64, i32, vp, ctypes.c_size_t, vp]
+    L.sct_bc_correct.restype = ctypes.c_int
+    L.sct_bc_correct.argtypes = [vp, i64, vp, i64, i32, vp, vp, vp]
+    L.sct_bc_pair_hist.restype = ctypes.c_int
+    L.sct_bc_pair_hist.argtypes = [vp, i64, i32, vp, vp]
+    _lib = L
+    return L
+
+
+def check(rc: int) -> None:
+    if rc != 0:
+        raise BarcodeError("sct_barcode error %d: %s" % (rc, load().sct_bc_last_error().decode("utf-8", "replace")))
+
+
+def _device(device=None):
+    """The torch device to run on; raises when there is no GPU (engine.py: no CPU fallback)."""
+    import torch
+
+    from sctools_amd import engine
+
+    if isinstance(device, int) or (isinstance(device, str) and device.isdigit()):
+        device = torch.device("cuda", int(device))
+    return engine._device(device)
+
+
+def _stream(dev):
+    import torch
+
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+
+
+def encode_array(raw: np.ndarray) -> np.ndarray:
+    """TwoBit codes (uint64) of an ``[n, L]`` uint8 array of upper-case ``ACGT`` bytes."""
+    n, length = raw.shape
+    codes = np.zeros(n, dtype=np.uint64)
+    for j in range(length):
+        codes = (codes << np.uint64(2)) | ((raw[:, j] >> 1) & 3).astype(np.uint64)  # A=0 C=1 T=2 G=3
+    return codes
+
+
+def pair_histogram(codes, barcode_length: int, device=None) -> np.ndarray:
+    """Number of unordered pairs of ``codes`` at each Hamming distance 0..32 (uint64 [33]), counted on
+    the GPU by ``sct_bc_pair_hist``."""
+    import torch
+
+    if barcode_length > MAX_PAIR_LENGTH:
+        raise ValueError("barcode_length %d exceeds the limit of %d bases (2 bits per base in 64 bits)"
+                         % (barcode_length, MAX_PAIR_LENGTH))
+    if barcode_length < 1:
+        raise ValueError("barcode_length must be a positive integer")
+    codes = np.ascontiguousarray(codes, dtype=np.uint64)
+    if codes.size > MAX_PAIR_BARCODES:
+        raise ValueError("%d barcodes exceed the pair kernel's limit of %d" % (codes.size, MAX_PAIR_BARCODES))
+    lib = load()
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        d_codes = torch.from_numpy(codes.view(np.int64)).to(dev)
+        hist = torch.empty(HIST_BINS, dtype=torch.int64, device=dev)
+        check(lib.sct_bc_pair_hist(_ptr(d_codes), int(codes.size), int(barcode_length), _ptr(hist), _stream(dev)))
+        return hist.cpu().numpy().view(np.uint64)
+
+
+def summary_from_histogram(hist) -> Mapping[str, float]:
+    """The six values of ``summarize_hamming_distances`` from the distance histogram: what
+    ``np.percentile(distances, [0, 25, 50, 75, 100])`` (linear interpolation between the order
+    statistics floor(q (N - 1)) and the next) and ``np.mean(distances)`` give on the N distances.
+    Every quartile is a small integer plus a multiple of 1/4, so the values are exact."""
+    counts = [int(c) for c in hist]
+    total = sum(counts)
+    cum = np.cumsum(np.array(counts, dtype=object))
+
+    def order_statistic(k: int) -> int:  # the k-th smallest distance, k in 0..total-1
+        return next(d for d, c in enumerate(cum) if c > k)
+
+    values = []
+    for quarter in range(5):
+        lo, rem = divmod(quarter * (total - 1), 4)
+        v_lo, v_hi = order_statistic(lo), order_statistic(min(lo + 1, total - 1))
+        values.append(np.float64(v_lo + (v_hi - v_lo) * rem / 4))
+    values.append(np.float64(sum(d * c for d, c in enumerate(counts))) / np.float64(total))
+    return dict(zip(("minimum", "25th percentile", "median", "75th percentile", "maximum", "average"), values))
+
+
+def base4_entropy(x: np.ndarray, axis: int = 1) -> np.ndarray:
+    """Entropy in base four of the observation counts along ``axis``, in [0, 1] (stats.py:24-55)."""
+    totals = np.sum(x, axis=axis)
+    p = np.divide(x, totals[:, None] if axis == 1 else totals)
+    with np.errstate(divide="ignore"):
+        r = np.log(p) / np.log(4)
+    r[np.isinf(r)] = 0  # 0 * log(0) = 0
+    return np.abs(-1 * np.sum(p * r, axis=axis))
+
+
+class Barcodes:
+    """A set of nucleotide barcodes in 2-bit code, mapped to the number of times each was seen.
+
+    Parameters
+    ----------
+    barcodes: Mapping[int, int]
+        2-bit encoded barcode -> observation count
+    barcode_length: int
+        the length of every barcode in the set
+    """
+
+    def __init__(self, barcodes: Mapping, barcode_length: int):
+        if not isinstance(barcodes, Mapping):
+            raise TypeError('The argument "barcodes" must be a dict-like object mapping barcodes to counts')
+        self._mapping = barcodes
+        if not isinstance(barcode_length, int) and barcode_length > 0:  # (the reference's check, barcode.py:57)
+            raise ValueError('The argument "barcode_length" must be a positive integer')
+        self._barcode_length = barcode_length
+
+    def __contains__(self, item) -> bool:
+        return item in self._mapping
+
+    def __iter__(self) -> Iterator:
+        return iter(self._mapping)
+
+    def __len__(self) -> int:
+        return len(self._mapping)
+
+    def __getitem__(self, item) -> int:
+        return self._mapping[item]
+
+    def summarize_hamming_distances(self, device=None) -> Mapping[str, float]:
+        """minimum, 25th percentile, median, 75th percentile, maximum and average Hamming distance
+        over all pairs of barcodes (barcode.py:73-103), from the GPU's all-pairs histogram."""
+        if self._barcode_length > MAX_PAIR_LENGTH:
+            raise ValueError("barcode_length %d exceeds the limit of %d bases (2 bits per base in 64 bits)"
+                             % (self._barcode_length, MAX_PAIR_LENGTH))
+        keys = ("minimum", "25th percentile", "median", "75th percentile", "maximum", "average")
+        if len(self) < 2:  # no pair: numpy decides what the summary of nothing is, as in the reference
+            distances = []
+            values = list(np.percentile(distances, [0, 25, 50, 75, 100]))
+            values.append(np.mean(distances))
+            return dict(zip(keys, values))
+        codes = np.fromiter(self._mapping.keys(), dtype=np.uint64, count=len(self))
+        return summary_from_histogram(pair_histogram(codes, self._barcode_length, device))
+
+    def base_frequency(self, weighted=False) -> np.ndarray:
+        """``[barcode_length, 4]`` uint64: how many barcodes hold base code 0..3 (A, C, T, G) at each
+        position (barcode.py:105-147)."""
+        if weighted:
+            raise NotImplementedError
+        counts = np.zeros((self._barcode_length, 4), dtype=np.uint64)
+        keys = np.fromiter(self._mapping.keys(), dtype=np.uint64)
+        for i in reversed(range(self._barcode_length)):
+            counts[i] = np.bincount((keys & np.uint64(3)).astype(np.int64), minlength=4)
+            keys = keys >> np.uint64(2)
+        return counts
+
+    def effective_diversity(self, weighted=False) -> np.ndarray:
+        """Base-4 entropy of the base frequencies at each position; 1 is an even split."""
+        return base4_entropy(self.base_frequency(weighted=weighted))
+
+    @classmethod
+    def from_whitelist(cls, file_: str, barcode_length: int):
+        """One barcode per line; every line loses its last byte (barcode.py:188-191)."""
+        with open(file_, "rb") as f:
+            return cls(Counter(TwoBit.encode(line[:-1]) for line in f), barcode_length)
+
+    @classmethod
+    def from_iterable_encoded(cls, iterable: Iterable[int], barcode_length: int):
+        return cls(Counter(iterable), barcode_length=barcode_length)
+
+    @classmethod
+    def from_iterable_strings(cls, iterable: Iterable[str], barcode_length: int):
+        return cls(Counter(TwoBit.encode(b.encode()) for b in iterable), barcode_length=barcode_length)
+
+    @classmethod
+    def from_iterable_bytes(cls, iterable: Iterable[bytes], barcode_length: int):
+        return cls(Counter(TwoBit.encode(b) for b in iterable), barcode_length=barcode_length)
+
+
+class _Whitelist:
+    """Host index of a whitelist file: barcode -> largest file index, and the lines in file order."""
+
+    def __init__(self, whitelist_file: str):
+        with open(whitelist_file, "r") as f:
+            self.barcodes = [line[:-1] for line in f]  # every line loses its last character (barcode.py:352-355)
+        self.length = len(self.barcodes[0]) if self.barcodes else 0
+        if self.length > MAX_CORRECT_LENGTH:
+            raise ValueError("whitelist barcodes of %d bases exceed the limit of %d (2 bits per base and one "
+                             "spare value in 64 bits)" % (self.length, MAX_CORRECT_LENGTH))
+        self.index = {}  # the ACGT barcodes of the whitelist's length: what the device table holds
+        self.other = {}  # the reference's error map of every other line: key -> file index
+        self.main_lines = []  # file indices of the barcodes in `index`, in file order
+        self.odd_lines = []  # file indices of the lines of the whitelist's length with a character outside ACGT
+        for i, barcode in enumerate(self.barcodes):
+            if len(barcode) == self.length and self.length > 0 and set(barcode) <= set("ACGT"):
+                self.index[barcode] = i
+                self.main_lines.append(i)
+                continue
+            if len(barcode) == self.length and self.length > 0:
+                self.odd_lines.append(i)
+            self.other[barcode] = i
+            for pos, base in enumerate(barcode):
+                for error in "ACGTN":
+                    if error != base:
+                        self.other[barcode[:pos] + error + barcode[pos + 1:]] = i
+
+    def lookup(self, barcode) -> int:
+        """File index of the corrected barcode: 1 + 3*L lookups (4 for a single N) and one in the side
+        map; KeyError if none."""
+        if not isinstance(barcode, str):
+            raise KeyError(barcode)
+        best = self.other.get(barcode, -1)
+        if len(barcode) == self.length and self.length:
+            odd = [pos for pos, base in enumerate(barcode) if base not in "ACGT"]
+            positions = ()
+            if not odd:
+                positions, best = range(self.length), max(best, self.index.get(barcode, -1))
+            elif len(odd) == 1 and barcode[odd[0]] == "N":
+                positions = odd
+            for pos in positions:
+                for base in "ACGT":
+                    if base != barcode[pos]:
+                        best = max(best, self.index.get(barcode[:pos] + base + barcode[pos + 1:], -1))
+        if best < 0:
+            raise KeyError(barcode)
+        return best
+
+    def codes(self) -> np.ndarray:
+        """TwoBit codes of the barcodes of the whitelist's length, in file order."""
+        text = "".join(self.barcodes[i] for i in self.main_lines).encode("ascii")
+        return encode_array(np.frombuffer(text, dtype=np.uint8).reshape(len(self.main_lines), self.length))
+
+
+class ErrorsToCorrectBarcodesMap:
+    """Correct any barcode that is within Hamming distance 1 of a whitelisted barcode.
+
+    ``ErrorsToCorrectBarcodesMap(mapping)`` uses the mapping as the reference does;
+    :meth:`single_hamming_errors_from_whitelist` is the GPU path.
+    """
+
+    def __init__(self, errors_to_barcodes: Mapping[str, str]):
+        if not isinstance(errors_to_barcodes, Mapping):
+            raise TypeError('The argument "errors_to_barcodes" must be a mapping of erroneous barcodes to correct '
+                            "barcodes, not %s" % type(errors_to_barcodes))
+        self._map = errors_to_barcodes
+        self._whitelist: Optional[_Whitelist] = None
+        self._device_arg = None
+        self._tables = {}  # torch device -> (table, device index -> file index or None)
+
+    @classmethod
+    def single_hamming_errors_from_whitelist(cls, whitelist_file: str, device=None):
+        """From a text file of one barcode per line (barcode.py:337-355).  Keeps a host index of the
+        whitelist and no error dict; the device table is built on the first array or BAM call."""
+        self = cls({})
+        self._map = None
+        self._whitelist = _Whitelist(whitelist_file)
+        self._device_arg = device
+        return self
+
+    @property
+    def barcode_length(self) -> int:
+        """Length of the whitelist's barcodes (its first line's)."""
+        return self._require_whitelist().length
+
+    @property
+    def whitelist(self):
+        """The whitelist's lines in file order: ``whitelist[index]`` is the barcode of a returned index."""
+        return self._require_whitelist().barcodes
+
+    def _require_whitelist(self) -> _Whitelist:
+        if self._whitelist is None:
+            raise TypeError("this map was built from a Mapping; array correction needs "
+                            "single_hamming_errors_from_whitelist")
+        return self._whitelist
+
+    def get_corrected_barcode(self, barcode: str) -> str:
+        """The barcode if it is whitelisted, its correction if it is within distance 1 of the
+        whitelist, else ``KeyError`` (barcode.py:284-308).  Answered on the host."""
+        if self._whitelist is None:
+            return self._map[barcode]
+        return self._whitelist.barcodes[self._whitelist.lookup(barcode)]
+
+    # ---- device ----
+    def _table(self, dev):
+        import torch
+
+        if dev in self._tables:
+            return self._tables[dev]
+        wl = self._require_whitelist()
+        if wl.length < 1:
+            raise ValueError("the whitelist's first line is empty: there is no barcode length to correct to")
+        lib = load()
+        n = len(wl.main_lines)
+        with torch.cuda.device(dev):
+            codes = torch.from_numpy(wl.codes().view(np.int64)).to(dev)
+            nbytes = ctypes.c_size_t(0)
+            check(lib.sct_bc_table_size(n, ctypes.byref(nbytes)))
+            table = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
+            check(lib.sct_bc_table_build(_ptr(codes), n, wl.length, ctypes.c_void_p(table.data_ptr()), table.numel(),
+                                         _stream(dev)))
+            lines = None
+            if n != len(wl.barcodes):  # lines of another length shift the file indices
+                lines = torch.tensor(wl.main_lines + [-1], dtype=torch.int32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()  # `codes` may be freed
+        self._tables[dev] = (table, lines)
+        return self._tables[dev]
+
+    def correct_barcodes(self, raw, return_corrected: bool = False):
+        """Correct a column of raw barcodes on the GPU (``sct_bc_correct``).
+
+        ``raw`` is a numpy ``S<L>`` array, a numpy ``uint8 [n, L]`` array, or a ``uint8 [n, L]`` torch
+        tensor on the host or on the device.  Returns the int32 whitelist file indices of the
+        corrected barcodes (-1 where ``get_corrected_barcode`` raises ``KeyError``) and, with
+        ``return_corrected``, the ``[n, L]`` uint8 corrected bytes (the raw bytes where there is no
+        correction), as numpy arrays for numpy input and as tensors on the input's device otherwise.
+        """
+        wl = self._require_whitelist()
+        import torch
+
+        length = wl.length
+        as_numpy = isinstance(raw, np.ndarray)
+        if as_numpy:
+            if raw.dtype.kind == "S":
+                if raw.dtype.itemsize != length or raw.ndim != 1:
+                    raise ValueError("expected a 1-d S%d array, got %s %s" % (length, raw.dtype, raw.shape))
+                raw = np.ascontiguousarray(raw).view(np.uint8).reshape(raw.shape[0], length)
+            if raw.dtype != np.uint8 or raw.ndim != 2 or raw.shape[1] != length:
+                raise ValueError("expected a uint8 [n, %d] array, got %s %s" % (length, raw.dtype, raw.shape))
+            t = torch.from_numpy(np.ascontiguousarray(raw))
+        elif isinstance(raw, torch.Tensor):
+            if raw.dtype != torch.uint8 or raw.dim() != 2 or raw.shape[1] != length:
+                raise ValueError("expected a uint8 [n, %d] tensor, got %s %s" % (length, raw.dtype, tuple(raw.shape)))
+            t = raw
+        else:
+            raise TypeError("raw must be a numpy array or a torch tensor, not %s" % type(raw))
+        dev = t.device if t.is_cuda else _device(self._device_arg)
+        lib = load()
+        table, lines = self._table(dev)
+        with torch.cuda.device(dev):
+            d_raw = t.to(dev).contiguous()  # a strided view is copied, never read through its strides
+            n = int(d_raw.shape[0])
+            index = torch.empty(n, dtype=torch.int32, device=dev)
+            corrected = torch.empty((n, length), dtype=torch.uint8, device=dev) if return_corrected else None
+            check(lib.sct_bc_correct(ctypes.c_void_p(table.data_ptr()), len(wl.main_lines), _ptr(d_raw), n, length,
+                                     _ptr(index), _ptr(corrected), _stream(dev)))
+            if lines is not None:
+                index = lines[index.long()]  # -1 picks the trailing -1
+            for i in wl.odd_lines:  # the few lines the table cannot hold (a character outside ACGT)
+                index, corrected = self._match_odd_line(d_raw, i, index, corrected)
+        outs = (index, corrected) if return_corrected else (index,)
+        if not t.is_cuda:
+            outs = tuple(o.cpu() for o in outs)
+        if as_numpy:
+            outs = tuple(o.numpy() for o in outs)
+        return outs if return_corrected else outs[0]
+
+    def _match_odd_line(self, d_raw, line: int, index, corrected):
+        """Whitelist line ``line`` holds a character outside ACGT, so the table's 2-bit codes cannot
+        hold it: the queries it corrects by the reference's rule (equal to it, or differing in one
+        position by one of ``ACGTN``) get its file index where that is the larger one."""
+        import torch
+
+        entry = torch.tensor(list(self._whitelist.barcodes[line].encode("utf-8")), dtype=torch.uint8, device=d_raw.device)
+        differs = d_raw != entry
+        acgtn = torch.zeros(256, dtype=torch.bool, device=d_raw.device)
+        acgtn[list(b"ACGTN")] = True
+        n_diff = differs.sum(dim=1)
+        hit = (n_diff == 0) | ((n_diff == 1) & ~(differs & ~acgtn[d_raw.long()]).any(dim=1))
+        hit &= index < line
+        index = torch.where(hit, torch.full_like(index, line), index)
+        if corrected is not None:
+            corrected = torch.where(hit[:, None], entry[None, :], corrected)
+        return index, corrected
+
+    def correct_bam(self, bam_file: str, output_bam_file: str, level: int = 6) -> None:
+        """Write ``bam_file`` to ``output_bam_file`` with ``CB`` set to the corrected ``CR`` of every
+        record, or to the raw ``CR`` where there is no correction (barcode.py:357-379).  The records
+        are read and written natively on the host (``sct_bam_tag_*``), the lookups are one
+        ``sct_bc_correct`` call.  A record without ``CR`` raises ``KeyError`` before anything runs
+        on the GPU and before the output file exists."""
+        from sctools_amd import bamnative
+
+        wl = self._whitelist
+        length = wl.length if wl is not None else 0
+        with bamnative.TagColumn(bam_file, consts.RAW_CELL_BARCODE_TAG_KEY, consts.CELL_BARCODE_TAG_KEY,
+                                 length) as column:
+            others = None
+            if wl is None or wl.other or not length:  # values that only a host map can correct
+                others = []
+                for value in column.others():
+                    try:
+                        others.append(self.get_corrected_barcode(value))
+                    except KeyError:
+                        others.append(value)
+            values = column.values()
+            if length and values.shape[0]:
+                _, values = self.correct_barcodes(values, return_corrected=True)
+            column.write(output_bam_file, values, others, level=level)

@@ -1,0 +1,57 @@
+// bamwrite.h -- the BGZF writer path of libsct_bam.so's whole-file outputs (sct_bam_write_order,
+// sct_bam_tag_write): the header in its own members, as htslib writes it, then the record bytes
+// in 0xff00-byte members deflated in parallel, then the EOF member.  Host C++ (zlib, OpenMP).
+#pragma once
+#include <omp.h>
+
+#include <algorithm>
+
+#include "../../include/sct_bam.h"
+#include "bgzf.h"
+
+namespace {
+
+inline int write_bam_file(const char* out_path, const std::string& header, const uint8_t* body, size_t body_bytes,
+                          int level, int n_threads) {
+  std::vector<z_stream> zs(n_threads);
+  for (auto& z : zs) {
+    memset(&z, 0, sizeof(z));
+    deflateInit2(&z, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY);
+  }
+  struct ZEnd {
+    std::vector<z_stream>& zs;
+    ~ZEnd() {
+      for (auto& z : zs) deflateEnd(&z);
+    }
+  } zend{zs};
+  FILE* f = fopen(out_path, "wb");
+  if (!f) return fail(SCT_BAM_EIO, "cannot create %s", out_path);
+  struct Closer {
+    FILE*& f;
+    ~Closer() {
+      if (f) fclose(f);
+    }
+  } closer{f};
+  int bad = 0;
+  for (int pass = 0; pass < 2; pass++) {
+    const uint8_t* src = pass == 0 ? (const uint8_t*)header.data() : body;
+    const size_t total = pass == 0 ? header.size() : body_bytes;
+    const size_t np = (total + kBgzfMaxInput - 1) / kBgzfMaxInput;
+    std::vector<std::vector<uint8_t>> z(np);
+#pragma omp parallel for num_threads(n_threads) schedule(dynamic, 1) reduction(| : bad)
+    for (long k = 0; k < (long)np; k++) {
+      const size_t o = (size_t)k * kBgzfMaxInput;
+      if (!bgzf_block(src + o, std::min(kBgzfMaxInput, total - o), level, zs[omp_get_thread_num()], z[k])) bad = 1;
+    }
+    if (bad) return fail(SCT_BAM_EIO, "deflate failed");
+    for (size_t k = 0; k < np; k++)
+      if (fwrite(z[k].data(), 1, z[k].size(), f) != z[k].size()) return fail(SCT_BAM_EIO, "cannot write %s", out_path);
+  }
+  if (fwrite(kBgzfEof, 1, sizeof(kBgzfEof), f) != sizeof(kBgzfEof)) return fail(SCT_BAM_EIO, "cannot write %s", out_path);
+  FILE* g = f;
+  f = nullptr;
+  if (fclose(g) != 0) return fail(SCT_BAM_EIO, "cannot close %s", out_path);
+  return SCT_BAM_OK;
+}
+
+}  // namespace

@@ -14,6 +14,10 @@ codes as the reference's ``GenericPlatform`` metric commands
   CreateCountMatrix -b BAM -o PREFIX -a GTF [-c TAG -m TAG -g TAG -n]   (platform.py:384-470)
   MergeCountMatrices -i PREFIX... -o STEM                              (platform.py:475-516)
 
+An addition: ``CorrectBarcodes -i BAM -o BAM --whitelist FILE [--device N]`` sets every record's
+``CB`` from its ``CR`` and the whitelist (``ErrorsToCorrectBarcodesMap.correct_bam``,
+barcode.py:357-379), which the reference reaches only through ``Attach10xBarcodes --whitelist``.
+
 New flags are optional only: ``--float-mode {welford,exact}``, ``--device``, ``--devices N``
 (spread the entity runs over GPUs 0..N-1, one host thread each; same output) and, on
 CalculateCellMetrics, ``--gene-output-filestem STEM`` (also write the gene rows of the same
@@ -197,6 +201,23 @@ class GenericPlatform:
         count.CountMatrix.merge_matrices(args.input_prefixes).save(args.output_stem)
         return 0
 
+    @classmethod
+    def correct_barcodes(cls, args: Iterable[str] = None) -> int:
+        """CorrectBarcodes (an addition): CB from CR and a whitelist, the lookups on the GPU."""
+        from sctools_amd import barcode
+
+        parser = argparse.ArgumentParser(description="Sets CB to the whitelist barcode within Hamming distance 1 "
+                                                     "of CR, or to CR itself where there is none")
+        parser.add_argument("-i", "--input-bam", required=True, help="input bamfile with CR tags")
+        parser.add_argument("-o", "--output-bam", required=True, help="output bamfile")
+        parser.add_argument("--whitelist", required=True, help="text file, one barcode per line")
+        parser.add_argument("--device", default=None, help="GPU index or torch device (default: current GPU)")
+        args = parser.parse_args(args) if args is not None else parser.parse_args()
+        corrector = barcode.ErrorsToCorrectBarcodesMap.single_hamming_errors_from_whitelist(args.whitelist,
+                                                                                            device=args.device)
+        corrector.correct_bam(args.input_bam, args.output_bam)
+        return 0
+
 
 class TenXV2(GenericPlatform):
     """The reference exposes the metric commands on TenXV2 too (platform.py:579)."""
@@ -212,4 +233,5 @@ COMMANDS = {
     "VerifyBamSort": GenericPlatform.verify_bam_sort,
     "CreateCountMatrix": GenericPlatform.bam_to_count_matrix,
     "MergeCountMatrices": GenericPlatform.merge_count_matrices,
+    "CorrectBarcodes": GenericPlatform.correct_barcodes,
 }
