@@ -9,10 +9,11 @@ BAMDEC := sctools_amd/libsct_bam.so
 CSVFMT := sctools_amd/libsct_csv.so
 GBAM := sctools_amd/libsct_gbam.so
 BARCODE := sctools_amd/libsct_barcode.so
+FASTQ := sctools_amd/libsct_fastq.so
 
 SI4 := tests/native/libsct_engine_si4.so
 
-all: $(ENGINE) $(BAMDEC) $(CSVFMT) $(GBAM) $(BARCODE) oracle/liboracle.so tests/native/libfxcheck.so $(SI4)
+all: $(ENGINE) $(BAMDEC) $(CSVFMT) $(GBAM) $(BARCODE) $(FASTQ) oracle/liboracle.so tests/native/libfxcheck.so $(SI4)
 
 $(ENGINE): $(SRC) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -o $@ $(SRC) -L/opt/rocm/lib -lrccl
@@ -30,6 +31,9 @@ $(GBAM): sctools_amd/csrc/gbam.hip sctools_amd/csrc/inflate.h sctools_amd/csrc/b
 $(BARCODE): sctools_amd/csrc/barcode.hip include/sct_barcode.h
 	$(HIPCC) $(HIPFLAGS) -o $@ sctools_amd/csrc/barcode.hip
 
+$(FASTQ): sctools_amd/csrc/fastq.hip include/sct_fastq.h
+	$(HIPCC) $(HIPFLAGS) -o $@ sctools_amd/csrc/fastq.hip
+
 $(CSVFMT): sctools_amd/csrc/csvfmt.cpp include/sct_csv.h
 	g++ -O3 -std=c++17 -fopenmp -fPIC -shared -Wall -o $@ sctools_amd/csrc/csvfmt.cpp -lz
 
@@ -40,6 +44,6 @@ tests/native/libfxcheck.so: tests/native/fxcheck.cpp sctools_amd/csrc/fixedpt.h
 	g++ -O2 -std=c++17 -ffp-contract=off -fPIC -shared -o $@ tests/native/fxcheck.cpp
 
 clean:
-	rm -f $(ENGINE) $(BAMDEC) $(CSVFMT) $(GBAM) $(BARCODE) oracle/liboracle.so tests/native/libfxcheck.so $(SI4)
+	rm -f $(ENGINE) $(BAMDEC) $(CSVFMT) $(GBAM) $(BARCODE) $(FASTQ) oracle/liboracle.so tests/native/libfxcheck.so $(SI4)
 
 .PHONY: all clean

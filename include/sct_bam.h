@@ -143,6 +143,36 @@ int sct_bam_tag_write(const sct_bam_tags_t* t, const char* out_path, const char*
 
 void sct_bam_tag_close(sct_bam_tags_t* t);
 
+/* bam.Tagger.tag's host side (bam.py:208-233: zip the tag generators with the records, set_tag
+ * every yielded tag, write): string tags attached to the records of a BAM from byte columns, a
+ * window of records at a time.
+ *
+ * sct_bam_attach_open inflates `in_path`, keeps its records until sct_bam_attach_close, and
+ * writes the input's header to `out_path` (BGZF at zlib `level`, members as sct_bam_write_order's;
+ * n_threads <= 0: all cores). */
+typedef struct sct_bam_attach sct_bam_attach_t;
+int sct_bam_attach_open(const char* in_path, const char* out_path, int32_t level, int32_t n_threads,
+                        sct_bam_attach_t** out);
+
+/* Number of records of the input. */
+int64_t sct_bam_attach_n(const sct_bam_attach_t* h);
+
+/* Writes the next `n` input records.  `tag_names` is 2 * n_tags characters.  For each record,
+ * every listed tag is set in order with pysam's set_tag semantics: the first existing occurrence
+ * of that tag is cut out and TAG:Z:value is appended as the last tag (so a tag listed twice keeps
+ * the later value); every other byte of the record is unchanged.  values[t] is n x strides[t]
+ * bytes, row-major; lengths[t] is int32[n], the bytes of row i that are the value, or NULL (as
+ * `lengths` itself may be) for "all strides[t]".  A length of -1 means record i does not get tag
+ * t.  If fewer than n records remain in the input it writes those; *n_written (if set) is the
+ * number written.  Nothing is appended when the call returns an error. */
+int sct_bam_attach_write(sct_bam_attach_t* h, int64_t n, int32_t n_tags, const char* tag_names,
+                         const uint8_t* const* values, const int64_t* strides, const int32_t* const* lengths,
+                         int64_t* n_written);
+
+/* Writes the last member and the EOF member, closes the output and frees the handle.  The input
+ * records that no call wrote are not copied (the zip of bam.py:229 ends with its shortest input). */
+int sct_bam_attach_close(sct_bam_attach_t* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,6 @@
 """python -m sctools_amd <Command> [args]  (CalculateCellMetrics, CalculateGeneMetrics,
-MergeCellMetrics, MergeGeneMetrics, CreateCountMatrix, MergeCountMatrices, CorrectBarcodes)."""
+MergeCellMetrics, MergeGeneMetrics, SplitBam, TagSortBam, VerifyBamSort, CreateCountMatrix,
+MergeCountMatrices, CorrectBarcodes, Attach10xBarcodes, AttachBarcodes)."""
 import sys
 
 from sctools_amd.platform import COMMANDS

@@ -25,7 +25,10 @@ multi-threaded decoder (``sctools_amd/csrc/bamdec.cpp``).
 (``sctools_amd/csrc/bamsplit.cpp``).  ``TagSortableRecord`` / ``verify_sort`` /
 ``sort_by_tags_and_queryname`` mirror the reference's sort order on record objects
 (``bam.py:602-728``); ``verify_bam_sort`` checks a whole BAM on the GPU (VerifyBamSort) and
-``tag_sort_bam`` writes one in that order (TagSortBam).
+``tag_sort_bam`` writes one in that order (TagSortBam).  ``Tagger`` attaches tags from generators to
+the records of a BAM (``bam.py:185-233``): barcode generators that have ``columns()`` extract on the
+GPU, any other iterable is consumed on the host, and one native writer rewrites the records
+(``sct_bam_attach_*``).
 """
 
 import math
@@ -40,7 +43,7 @@ from sctools_amd import consts
 
 __all__ = ["BamRecord", "open_alignments", "read_header", "split", "get_barcodes_from_bam",
            "get_barcode_for_alignment", "SortError", "TagSortableRecord", "get_tag_or_default",
-           "sort_by_tags_and_queryname", "verify_sort", "verify_bam_sort", "tag_sort_bam"]
+           "sort_by_tags_and_queryname", "verify_sort", "verify_bam_sort", "tag_sort_bam", "Tagger"]
 
 _CIGAR_OPS = "MIDNSHP=X"
 _SEQ_NT16 = "=ACMGRSVTWYHKDBN"
@@ -610,3 +613,140 @@ def tag_sort_bam(in_bam: str, out_bam: str, tag_keys, device=None, level: int = 
     tie = torch.from_numpy(np.ascontiguousarray(qrank, dtype=np.int32)).to(eng.device)
     out = eng.tag_sort(cols, dims, order, tie, len(qnames))
     bamnative.write_order(in_bam, out_bam, out["pos"].to(torch.int64).cpu().numpy(), level=level)
+
+
+# ---- Tagger (bam.py:185-233) ----
+
+_HOST_BATCH = 1 << 16  # records per window of a host iterable
+
+
+def _host_windows(tag_sets, batch: int = _HOST_BATCH):
+    """Windows of a host iterable of tag sets (lists of ``(tag, value, "Z")``) in column form: ``(n, columns)``,
+    ``columns`` a list of ``(tag, uint8 [n, stride], int32 [n] lengths)`` with -1 where a record does not
+    carry the tag.  The
+    columns keep every record's tag order; a record whose order contradicts the window's starts a
+    new window."""
+    import numpy as np
+
+    order, rows = [], []
+
+    def flush():
+        n = len(rows)
+        out = []
+        for key in order:
+            values = [row.get(key) for row in rows]
+            stride = max((len(v) for v in values if v is not None), default=0)
+            col = np.zeros((n, stride), dtype=np.uint8)
+            lengths = np.full(n, -1, dtype=np.int32)
+            for i, v in enumerate(values):
+                if v is not None:
+                    lengths[i] = len(v)
+                    col[i, :len(v)] = np.frombuffer(v, dtype=np.uint8)
+            out.append((key[0], col, lengths))
+        del order[:], rows[:]
+        return n, out
+
+    for tag_set in tag_sets:
+        row, seen = {}, {}
+        for tag, value, *kind in tag_set:
+            if kind and kind[0] != "Z":
+                raise ValueError("Tagger attaches string (Z) tags only, got %r for %s" % (kind[0], tag))
+            if isinstance(tag, bytes):
+                tag = tag.decode()
+            seen[tag] = seen.get(tag, 0) + 1
+            row[(tag, seen[tag])] = value.encode() if isinstance(value, str) else bytes(value)
+        for attempt in range(2):
+            pos, trial = -1, list(order)
+            for key in row:
+                if key in trial:
+                    at = trial.index(key)
+                    if at <= pos:
+                        break
+                    pos = at
+                else:
+                    pos += 1
+                    trial.insert(pos, key)
+            else:
+                order[:] = trial
+                break
+            yield flush()  # this record lists its tags in another order than the window's
+        rows.append(row)
+        if len(rows) >= batch:
+            yield flush()
+    if rows:
+        yield flush()
+
+
+def _device_windows(generator, device, max_records):
+    """The windows of ``generator.columns()`` in the column form of :func:`_host_windows`."""
+    import numpy as np
+
+    for window in generator.columns(device=device, max_records=max_records):
+        out = []
+        for key, values in window.items():
+            if len(key) != 2:
+                continue  # "CB_index"
+            values = values.cpu().numpy()
+            lengths = None
+            index = window.get(key + "_index")
+            if index is not None:  # the tag goes only to the records that have a correction
+                lengths = np.where(index.cpu().numpy() < 0, -1, values.shape[1]).astype(np.int32)
+            out.append((key, values, lengths))
+        yield (out[0][1].shape[0] if out else 0), out
+
+
+class Tagger:
+    """Attaches the tags that generators yield to the records of a BAM, in step.
+
+    Parameters
+    ----------
+    bam_file : str
+        the BAM whose records receive the tags
+    device : optional
+        GPU index or torch device for the generators that extract on the GPU (default: current GPU)
+    """
+
+    def __init__(self, bam_file: str, device=None) -> None:
+        if not isinstance(bam_file, str):
+            raise TypeError(f'The argument "bam_file" must be of type str, not {type(bam_file)}')
+        self.bam_file = bam_file
+        self.device = device
+
+    def tag(self, output_bam_name: str, tag_generators) -> None:
+        """Writes the records of ``bam_file`` to ``output_bam_name`` with the tags of every generator
+        set, record k getting the k-th tag set of each; the output ends with the shortest of the
+        inputs.  A generator with ``columns()`` runs on the GPU, any other iterable on the host."""
+        import itertools
+
+        from sctools_amd import bamnative
+
+        with bamnative.TagAttacher(self.bam_file, output_bam_name) as out:
+            # the reference's zip advances every generator once more than the BAM has records before it
+            # ends; a bad FASTQ record beyond that one is never read there, and is not looked at here
+            sources = []
+            for g in tag_generators:
+                if hasattr(g, "columns") and getattr(g, "supports_columns", True):
+                    sources.append(_device_windows(g, self.device, out.n + 1))
+                else:
+                    sources.append(_host_windows(itertools.islice(g, out.n + 1)))
+            held = [(0, [], 0)] * len(sources)  # per source: (rows, columns, rows already written)
+            while out.remaining > 0:
+                n = out.remaining
+                for k, source in enumerate(sources):
+                    while held[k][2] >= held[k][0]:  # used up: the next window that has rows
+                        window = next(source, None)
+                        if window is None:
+                            n = 0  # the zip ends with its shortest input
+                            break
+                        held[k] = (window[0], window[1], 0)
+                    n = min(n, held[k][0] - held[k][2])
+                    if n == 0:
+                        break
+                if n == 0:
+                    break
+                columns = []
+                for k, (rows, window, at) in enumerate(held):
+                    for tag, values, lengths in window:
+                        columns.append((tag, values[at:at + n], None if lengths is None else lengths[at:at + n]))
+                    held[k] = (rows, window, at + n)
+                out.write(columns, n)

@@ -30,7 +30,8 @@ CELL_METRICS, GENE_METRICS, COUNT_MATRIX, SORT_KEYS = 0, 1, 2, 3
 _MODES = {"cell": CELL_METRICS, "gene": GENE_METRICS, "count": COUNT_MATRIX, "sortkeys": SORT_KEYS}
 EXPORTED = ("sct_bam_decode", "sct_bam_decode_tags", "sct_bam_last_error", "sct_bam_n", "sct_bam_column", "sct_bam_dictionary",
             "sct_bam_close", "sct_bam_split", "sct_bam_write_order", "sct_bam_tag_collect", "sct_bam_tag_n",
-            "sct_bam_tag_values", "sct_bam_tag_others", "sct_bam_tag_write", "sct_bam_tag_close")
+            "sct_bam_tag_values", "sct_bam_tag_others", "sct_bam_tag_write", "sct_bam_tag_close",
+            "sct_bam_attach_open", "sct_bam_attach_n", "sct_bam_attach_write", "sct_bam_attach_close")
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -80,6 +81,16 @@ def load() -> ctypes.CDLL:
     L.sct_bam_tag_write.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, vp, ctypes.c_char_p, vp, i32, i32]
     L.sct_bam_tag_close.restype = None
     L.sct_bam_tag_close.argtypes = [vp]
+    L.sct_bam_attach_open.restype = ctypes.c_int
+    L.sct_bam_attach_open.argtypes = [ctypes.c_char_p, ctypes.c_char_p, i32, i32, ctypes.POINTER(vp)]
+    L.sct_bam_attach_n.restype = ctypes.c_int64
+    L.sct_bam_attach_n.argtypes = [vp]
+    L.sct_bam_attach_write.restype = ctypes.c_int
+    L.sct_bam_attach_write.argtypes = [vp, ctypes.c_int64, i32, ctypes.c_char_p, ctypes.POINTER(vp),
+                                       ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(vp),
+                                       ctypes.POINTER(ctypes.c_int64)]
+    L.sct_bam_attach_close.restype = ctypes.c_int
+    L.sct_bam_attach_close.argtypes = [vp]
     _lib = L
     return L
 
@@ -233,3 +244,81 @@ class TagColumn:
                                          oo.ctypes.data if oo is not None else None, int(level), int(threads))
         if rc != OK:
             raise _EXC.get(rc, RuntimeError)(self._lib.sct_bam_last_error().decode("utf-8", "replace"))
+
+
+class TagAttacher:
+    """sct_bam_attach_*: the records of ``in_path`` written to ``out_path`` with string tags set from
+    byte columns, a window of records at a time (``bam.Tagger.tag``).  A context manager; leaving it
+    on an exception removes the partly written output."""
+
+    def __init__(self, in_path: str, out_path: str, level: int = 6, threads: int = 0):
+        self._lib = load()
+        self._h = ctypes.c_void_p()
+        self.out_path = out_path
+        rc = self._lib.sct_bam_attach_open(os.fsencode(in_path), os.fsencode(out_path), int(level), int(threads),
+                                           ctypes.byref(self._h))
+        if rc != OK:
+            raise _EXC.get(rc, RuntimeError)(self._lib.sct_bam_last_error().decode("utf-8", "replace"))
+        self.n = int(self._lib.sct_bam_attach_n(self._h))
+        self.written = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        else:
+            self.abort()
+
+    @property
+    def remaining(self) -> int:
+        return self.n - self.written
+
+    def write(self, columns, n: Optional[int] = None) -> int:
+        """``columns`` is a list of ``(tag, values, lengths)``: ``values`` a uint8 ``[n, stride]`` array,
+        ``lengths`` an int32 ``[n]`` array (-1: the record does not get the tag) or None for "every
+        row is ``stride`` bytes".  Every column has the same n (given as ``n`` when there is no
+        column).  Returns the number of records written (fewer than n at the input's end)."""
+        keep = []
+        for tag, values, lengths in columns:
+            if len(tag) != 2:
+                raise ValueError("tags are two-character names: %r" % (tag,))
+            v = np.ascontiguousarray(values, dtype=np.uint8)
+            if v.ndim != 2 or (n is not None and v.shape[0] != n):
+                raise ValueError("the values of %s must be [%s, stride], got %s" % (tag, n, v.shape))
+            n = v.shape[0]
+            ln = None
+            if lengths is not None:
+                ln = np.ascontiguousarray(lengths, dtype=np.int32)
+                if ln.shape != (n,):
+                    raise ValueError("the lengths of %s must be [%d], got %s" % (tag, n, ln.shape))
+            keep.append((tag, v, ln))
+        k = len(keep)
+        n = n or 0
+        names = "".join(t for t, _, _ in keep).encode("ascii")
+        vals = (ctypes.c_void_p * max(k, 1))(*[v.ctypes.data if v.size else None for _, v, _ in keep])
+        strides = (ctypes.c_int64 * max(k, 1))(*[v.shape[1] for _, v, _ in keep])
+        lens = (ctypes.c_void_p * max(k, 1))(*[ln.ctypes.data if ln is not None and ln.size else None
+                                              for _, _, ln in keep])
+        done = ctypes.c_int64(0)
+        rc = self._lib.sct_bam_attach_write(self._h, n, k, names, vals, strides, lens, ctypes.byref(done))
+        if rc != OK:
+            raise _EXC.get(rc, RuntimeError)(self._lib.sct_bam_last_error().decode("utf-8", "replace"))
+        self.written += int(done.value)
+        return int(done.value)
+
+    def close(self) -> None:
+        if self._h:
+            h, self._h = self._h, ctypes.c_void_p()
+            rc = self._lib.sct_bam_attach_close(h)
+            if rc != OK:
+                raise _EXC.get(rc, RuntimeError)(self._lib.sct_bam_last_error().decode("utf-8", "replace"))
+
+    def abort(self) -> None:
+        """Close and remove the output."""
+        if self._h:
+            h, self._h = self._h, ctypes.c_void_p()
+            self._lib.sct_bam_attach_close(h)
+        if os.path.exists(self.out_path):
+            os.remove(self.out_path)

@@ -9,6 +9,10 @@
 // new one appended as the last tag (pysam's set_tag), every other byte as it was -- and hands the
 // stream to the writer of sct_bam_write_order (bamwrite.h).  The inflated records stay in memory
 // between the passes, as they do for TagSortBam.
+//
+// sct_bam_attach_* is bam.Tagger.tag's host side (bam.py:208-233): the input is inflated once, then
+// every call rebuilds the next n records with the listed string tags set from byte columns and
+// appends them to the output, whose BGZF members are written as they fill (bamwrite.h).
 #include <fcntl.h>
 #include <omp.h>
 #include <stdlib.h>
@@ -35,6 +39,14 @@ struct sct_bam_tags {
   std::vector<uint8_t> fits;    // 1 where it has
   std::vector<int64_t> other_rec, other_off;  // records whose value has another length, and their values
   std::string other_bytes;
+};
+
+struct sct_bam_attach {
+  std::vector<uint8_t> data;     // the whole inflated input
+  std::vector<uint64_t> starts;  // record starts (at the block_size field) in data
+  int64_t next = 0;              // the next input record to write
+  int n_threads = 1;
+  BamStreamWriter writer;
 };
 
 namespace {
@@ -274,5 +286,134 @@ int sct_bam_tag_write(const sct_bam_tags_t* h, const char* out_path, const char*
 }
 
 void sct_bam_tag_close(sct_bam_tags_t* h) { delete h; }
+
+// ---- bam.Tagger.tag (bam.py:208-233): string tags attached from columns, a window at a time ----
+
+int sct_bam_attach_open(const char* in_path, const char* out_path, int32_t level, int32_t n_threads,
+                        sct_bam_attach_t** out) {
+  g_err.clear();
+  if (out) *out = nullptr;
+  if (!in_path || !out_path || !out) return fail(SCT_BAM_EIO, "NULL argument");
+  if (level < 0 || level > 9) return fail(SCT_BAM_EIO, "compression level %d outside 0..9", level);
+  if (n_threads <= 0) n_threads = omp_get_max_threads();
+  std::unique_ptr<sct_bam_attach> h(new sct_bam_attach);
+  h->n_threads = n_threads;
+  int rc = inflate_file(in_path, h->data, n_threads);
+  if (rc) return rc;
+  const uint8_t* d = h->data.data();
+  const size_t len = h->data.size();
+  if (len < 12 || memcmp(d, "BAM\1", 4) != 0) return fail(SCT_BAM_EFORMAT, "%s is not a BAM file", in_path);
+  size_t off = 8 + (size_t)rd32(d + 4);
+  if (off + 4 > len) return fail(SCT_BAM_EFORMAT, "truncated BAM header in %s", in_path);
+  const uint32_t n_ref = rd32(d + off);
+  off += 4;
+  for (uint32_t r = 0; r < n_ref; r++) {
+    if (off + 4 > len) return fail(SCT_BAM_EFORMAT, "truncated BAM header in %s", in_path);
+    off += 4 + (size_t)rd32(d + off) + 4;
+  }
+  if (off > len) return fail(SCT_BAM_EFORMAT, "truncated BAM header in %s", in_path);
+  const std::string header((const char*)d, off);
+  while (off + 4 <= len) {
+    const uint32_t bs = rd32(d + off);
+    if (off + 4 + bs > len) break;
+    h->starts.push_back(off);
+    off += 4 + (size_t)bs;
+  }
+  if (off != len) return fail(SCT_BAM_EFORMAT, "truncated BAM record at the end of %s", in_path);
+  rc = h->writer.open(out_path, header, level, n_threads);
+  if (rc) return rc;
+  *out = h.release();
+  return SCT_BAM_OK;
+}
+
+int64_t sct_bam_attach_n(const sct_bam_attach_t* h) { return h ? (int64_t)h->starts.size() : 0; }
+
+int sct_bam_attach_write(sct_bam_attach_t* h, int64_t n, int32_t n_tags, const char* tag_names,
+                         const uint8_t* const* values, const int64_t* strides, const int32_t* const* lengths,
+                         int64_t* n_written) {
+  g_err.clear();
+  if (n_written) *n_written = 0;
+  if (!h || n < 0 || n_tags < 0) return fail(SCT_BAM_EIO, "NULL handle or negative count");
+  if (n_tags > 0 && (!tag_names || !values || !strides || strlen(tag_names) != 2 * (size_t)n_tags))
+    return fail(SCT_BAM_VALUEERROR, "tags are %d two-character names", n_tags);
+  const int64_t first = h->next;
+  const int64_t m = std::min<int64_t>(n, (int64_t)h->starts.size() - first);
+  for (int32_t t = 0; t < n_tags; t++) {
+    if (strides[t] < 0 || (m > 0 && strides[t] > 0 && !values[t])) return fail(SCT_BAM_EIO, "NULL values of tag %d", t);
+  }
+  const uint8_t* d = h->data.data();
+  const int T = h->n_threads;
+  std::vector<std::vector<uint8_t>> part(T);
+  int bad = 0;  // 1 malformed record, 2 NUL byte, 4 length outside -1..stride
+  // a loop over the T parts: every part is built whatever number of threads the runtime grants
+#pragma omp parallel for num_threads(T) schedule(static, 1) reduction(| : bad)
+  for (int tn = 0; tn < T; tn++) {
+    const int64_t lo = m * tn / T, hi = m * (tn + 1) / T;
+    std::vector<uint8_t>& o = part[tn];
+    std::vector<uint8_t> aux;
+    for (int64_t i = lo; i < hi; i++) {
+      const uint8_t* rec = d + h->starts[first + i];
+      const uint32_t bs = rd32(rec);
+      const uint8_t* b = rec + 4;
+      uint64_t p = 32;
+      if (bs >= 32) p += (uint64_t)b[8] + 4ull * rd16(b + 12) + ((uint64_t)rd32(b + 16) + 1) / 2 + rd32(b + 16);
+      if (bs < 32 || p > bs) {
+        bad |= 1;
+        continue;
+      }
+      aux.assign(b + p, b + bs);
+      for (int32_t t = 0; t < n_tags; t++) {
+        const int64_t vl = lengths && lengths[t] ? (int64_t)lengths[t][i] : strides[t];
+        if (vl == -1) continue;  // record i does not get tag t
+        if (vl < 0 || vl > strides[t]) {
+          bad |= 4;
+          continue;
+        }
+        const uint8_t* v = values[t] + (size_t)i * strides[t];
+        if (vl && memchr(v, 0, (size_t)vl)) bad |= 2;
+        // set_tag: the first occurrence is cut out, the new value goes last
+        size_t q = 0;
+        while (q + 3 <= aux.size()) {
+          const size_t w = read_tag(aux.data() + q + 3, aux.data() + aux.size(), (char)aux[q + 2], nullptr);
+          if (!w) {
+            bad |= 1;
+            break;
+          }
+          if (aux[q] == (uint8_t)tag_names[2 * t] && aux[q + 1] == (uint8_t)tag_names[2 * t + 1]) {
+            aux.erase(aux.begin() + (ptrdiff_t)q, aux.begin() + (ptrdiff_t)(q + 3 + w));
+            break;
+          }
+          q += 3 + w;
+        }
+        aux.push_back((uint8_t)tag_names[2 * t]);
+        aux.push_back((uint8_t)tag_names[2 * t + 1]);
+        aux.push_back('Z');
+        aux.insert(aux.end(), v, v + vl);
+        aux.push_back(0);
+      }
+      const uint32_t nbs = (uint32_t)(p + aux.size());
+      const uint8_t* nb = (const uint8_t*)&nbs;
+      o.insert(o.end(), nb, nb + 4);
+      o.insert(o.end(), b, b + p);
+      o.insert(o.end(), aux.begin(), aux.end());
+    }
+  }
+  if (bad & 1) return fail(SCT_BAM_EFORMAT, "malformed BAM record among records %lld..%lld", (long long)first, (long long)(first + m));
+  if (bad & 4) return fail(SCT_BAM_VALUEERROR, "a tag length is outside -1..stride");
+  if (bad & 2) return fail(SCT_BAM_VALUEERROR, "a tag value holds a NUL byte");
+  std::vector<uint8_t>& pending = h->writer.pending();
+  for (int tn = 0; tn < T; tn++) pending.insert(pending.end(), part[tn].begin(), part[tn].end());
+  h->next += m;
+  if (n_written) *n_written = m;
+  return h->writer.flush_full();
+}
+
+int sct_bam_attach_close(sct_bam_attach_t* h) {
+  g_err.clear();
+  if (!h) return SCT_BAM_OK;
+  const int rc = h->writer.finish();
+  delete h;
+  return rc;
+}
 
 }  // extern "C"

@@ -54,4 +54,75 @@ inline int write_bam_file(const char* out_path, const std::string& header, const
   return SCT_BAM_OK;
 }
 
+// The same layout written piece by piece (sct_bam_attach_*): open() writes the header members,
+// append() takes record bytes and writes every full 0xff00-byte member (deflated in parallel),
+// keeping the rest for the next call, so the members do not depend on how the caller cut the
+// stream; finish() writes the last partial member and the EOF member.
+class BamStreamWriter {
+ public:
+  ~BamStreamWriter() {
+    for (auto& z : zs_) deflateEnd(&z);
+    if (f_) fclose(f_);
+  }
+  int open(const char* out_path, const std::string& header, int level, int n_threads) {
+    path_ = out_path;
+    level_ = level;
+    n_threads_ = n_threads;
+    zs_.resize(n_threads);
+    for (auto& z : zs_) {
+      memset(&z, 0, sizeof(z));
+      deflateInit2(&z, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY);
+    }
+    f_ = fopen(out_path, "wb");
+    if (!f_) return fail(SCT_BAM_EIO, "cannot create %s", out_path);
+    const int rc = write_members((const uint8_t*)header.data(), header.size());
+    if (rc) {  // the file this call created is not left behind with part of a header
+      fclose(f_);
+      f_ = nullptr;
+      remove(out_path);
+    }
+    return rc;
+  }
+  std::vector<uint8_t>& pending() { return pending_; }
+  // writes the full members of pending()
+  int flush_full() {
+    const size_t full = pending_.size() / kBgzfMaxInput * kBgzfMaxInput;
+    if (!full) return SCT_BAM_OK;
+    const int rc = write_members(pending_.data(), full);
+    pending_.erase(pending_.begin(), pending_.begin() + (ptrdiff_t)full);
+    return rc;
+  }
+  int finish() {
+    int rc = write_members(pending_.data(), pending_.size());
+    pending_.clear();
+    if (rc) return rc;
+    if (fwrite(kBgzfEof, 1, sizeof(kBgzfEof), f_) != sizeof(kBgzfEof)) return fail(SCT_BAM_EIO, "cannot write %s", path_.c_str());
+    FILE* g = f_;
+    f_ = nullptr;
+    if (fclose(g) != 0) return fail(SCT_BAM_EIO, "cannot close %s", path_.c_str());
+    return SCT_BAM_OK;
+  }
+
+ private:
+  int write_members(const uint8_t* src, size_t total) {
+    const size_t np = (total + kBgzfMaxInput - 1) / kBgzfMaxInput;
+    std::vector<std::vector<uint8_t>> z(np);
+    int bad = 0;
+#pragma omp parallel for num_threads(n_threads_) schedule(dynamic, 1) reduction(| : bad)
+    for (long k = 0; k < (long)np; k++) {
+      const size_t o = (size_t)k * kBgzfMaxInput;
+      if (!bgzf_block(src + o, std::min(kBgzfMaxInput, total - o), level_, zs_[omp_get_thread_num()], z[k])) bad = 1;
+    }
+    if (bad) return fail(SCT_BAM_EIO, "deflate failed");
+    for (size_t k = 0; k < np; k++)
+      if (fwrite(z[k].data(), 1, z[k].size(), f_) != z[k].size()) return fail(SCT_BAM_EIO, "cannot write %s", path_.c_str());
+    return SCT_BAM_OK;
+  }
+  std::string path_;
+  int level_ = 6, n_threads_ = 1;
+  std::vector<z_stream> zs_;
+  std::vector<uint8_t> pending_;
+  FILE* f_ = nullptr;
+};
+
 }  // namespace

@@ -14,9 +14,13 @@ codes as the reference's ``GenericPlatform`` metric commands
   CreateCountMatrix -b BAM -o PREFIX -a GTF [-c TAG -m TAG -g TAG -n]   (platform.py:384-470)
   MergeCountMatrices -i PREFIX... -o STEM                              (platform.py:475-516)
 
+  Attach10xBarcodes --r1 FASTQ --u2 BAM -o BAM [--i1 FASTQ] [-w WHITELIST]                 (platform.py:579-758)
+  AttachBarcodes --r1 FASTQ --u2 BAM -o BAM [--i1 FASTQ] [-w WHITELIST]
+                 [--{sample,cell,molecule}-barcode-start-position N --{...}-barcode-length N]  (platform.py:761-1126)
+
 An addition: ``CorrectBarcodes -i BAM -o BAM --whitelist FILE [--device N]`` sets every record's
 ``CB`` from its ``CR`` and the whitelist (``ErrorsToCorrectBarcodesMap.correct_bam``,
-barcode.py:357-379), which the reference reaches only through ``Attach10xBarcodes --whitelist``.
+barcode.py:357-379), for a BAM that already carries ``CR``.
 
 New flags are optional only: ``--float-mode {welford,exact}``, ``--device``, ``--devices N``
 (spread the entity runs over GPUs 0..N-1, one host thread each; same output) and, on
@@ -30,7 +34,7 @@ Run as ``python -m sctools_amd <Command> [args]``.
 import argparse
 from typing import Iterable, Set
 
-from sctools_amd import bam, consts, count, gtf, metrics
+from sctools_amd import bam, consts, count, fastq, gtf, metrics
 
 
 def _engine_args(parser):
@@ -220,7 +224,157 @@ class GenericPlatform:
 
 
 class TenXV2(GenericPlatform):
-    """The reference exposes the metric commands on TenXV2 too (platform.py:579)."""
+    """10x Genomics v2: the metric commands (platform.py:579) and ``Attach10xBarcodes``.
+
+    The three barcodes of a 10x v2 read pair: cell and molecule barcode in read 1, the sample barcode in
+    the i7 index read, with the tags they are attached under.
+    """
+
+    cell_barcode = fastq.EmbeddedBarcode(start=0, end=16, quality_tag=consts.QUALITY_CELL_BARCODE_TAG_KEY,
+                                         sequence_tag=consts.RAW_CELL_BARCODE_TAG_KEY)
+    molecule_barcode = fastq.EmbeddedBarcode(start=16, end=26, quality_tag=consts.QUALITY_MOLECULE_BARCODE_TAG_KEY,
+                                             sequence_tag=consts.RAW_MOLECULE_BARCODE_TAG_KEY)
+    sample_barcode = fastq.EmbeddedBarcode(start=0, end=8, quality_tag=consts.QUALITY_SAMPLE_BARCODE_TAG_KEY,
+                                           sequence_tag=consts.RAW_SAMPLE_BARCODE_TAG_KEY)
+
+    @classmethod
+    def _tag_bamfile(cls, input_bamfile_name: str, output_bamfile_name: str, tag_generators, device=None) -> None:
+        bam.Tagger(input_bamfile_name, device=device).tag(output_bamfile_name, tag_generators)
+
+    @classmethod
+    def _make_tag_generators(cls, r1, i1=None, whitelist=None) -> list:
+        """Cell and molecule barcodes from ``r1`` (with ``CB`` when there is a whitelist), then the sample
+        barcode from ``i1`` (platform.py:653-704)."""
+        if whitelist is not None:
+            generators = [fastq.BarcodeGeneratorWithCorrectedCellBarcodes(
+                fastq_files=r1, embedded_cell_barcode=cls.cell_barcode, whitelist=whitelist,
+                other_embedded_barcodes=[cls.molecule_barcode])]
+        else:
+            generators = [fastq.EmbeddedBarcodeGenerator(
+                fastq_files=r1, embedded_barcodes=[cls.cell_barcode, cls.molecule_barcode])]
+        if i1 is not None:
+            generators.append(fastq.EmbeddedBarcodeGenerator(fastq_files=i1, embedded_barcodes=[cls.sample_barcode]))
+        return generators
+
+    @classmethod
+    def attach_barcodes(cls, args: Iterable[str] = None) -> int:
+        """Attach10xBarcodes (platform.py:706-758): the barcodes of the read 1 (and i7) FASTQ attached to
+        the records of the unaligned read 2 BAM; extraction and correction on the GPU."""
+        parser = argparse.ArgumentParser()
+        parser.add_argument("--r1", required=True, help="FASTQ of read 1 (10x v2): cell barcode in bases 0-15, molecule barcode in bases 16-25")
+        parser.add_argument("--u2", required=True, help="unaligned BAM of read 2 (the cDNA), one record per FASTQ record "
+                            "in the same order, e.g. from picard FastqToSam")
+        parser.add_argument("--i1", default=None, help="FASTQ of the i7 index read; when given, the sample barcode (bases 0-7) is attached too")
+        parser.add_argument("-o", "--output-bamfile", required=True, help="the tagged BAM to write")
+        parser.add_argument("-w", "--whitelist", default=None,
+                            help="cell barcode whitelist, one barcode per line; with it, CB is set where the raw cell "
+                                 "barcode is on the list or one substitution away from it")
+        parser.add_argument("--device", default=None, help="GPU index or torch device (default: current GPU)")
+        args = parser.parse_args(args) if args is not None else parser.parse_args()
+        cls._tag_bamfile(args.u2, args.output_bamfile, cls._make_tag_generators(args.r1, args.i1, args.whitelist),
+                         device=args.device)
+        return 0
+
+
+class BarcodePlatform(GenericPlatform):
+    """``AttachBarcodes`` (platform.py:761-1126): ``Attach10xBarcodes`` with the position and length of
+    the sample, cell and molecule barcode given on the command line."""
+
+    cell_barcode = None
+    molecule_barcode = None
+    sample_barcode = None
+
+    @classmethod
+    def _validate_barcode_args(cls, args):
+        """Every barcode has both a start position and a length or neither, a sample barcode has an i7
+        file to come from, and the molecule barcode starts at or after the cell barcode's end."""
+        cls._validate_barcode_length_and_position(args.cell_barcode_start_pos, args.cell_barcode_length)
+        cls._validate_barcode_length_and_position(args.molecule_barcode_start_pos, args.molecule_barcode_length)
+        cls._validate_barcode_length_and_position(args.sample_barcode_start_pos, args.sample_barcode_length)
+        if args.i1 is None and args.sample_barcode_length:
+            raise argparse.ArgumentError(None, "An i7 index fastq file must be given to attach a sample barcode")
+        if args.cell_barcode_length and args.molecule_barcode_length:
+            cls._validate_barcode_input(args.molecule_barcode_start_pos,
+                                        args.cell_barcode_start_pos + args.cell_barcode_length)
+        return args
+
+    @classmethod
+    def _validate_barcode_length_and_position(cls, barcode_start_position, barcode_length):
+        has_position = bool(barcode_start_position) or barcode_start_position == 0
+        if has_position != bool(barcode_length):
+            raise argparse.ArgumentError(
+                None, "Invalid position/length, both position and length must be provided by the user together")
+
+    @classmethod
+    def _validate_barcode_input(cls, given_value, min_value):
+        if given_value < min_value:
+            raise argparse.ArgumentTypeError("Invalid barcode length/position")
+        return given_value
+
+    @classmethod
+    def _validate_barcode_start_pos(cls, given_value):
+        return cls._validate_barcode_input(int(given_value), 0)
+
+    @classmethod
+    def _validate_barcode_length(cls, given_value):
+        return cls._validate_barcode_input(int(given_value), 1)
+
+    @classmethod
+    def _tag_bamfile(cls, input_bamfile_name: str, output_bamfile_name: str, tag_generators, device=None) -> None:
+        bam.Tagger(input_bamfile_name, device=device).tag(output_bamfile_name, tag_generators)
+
+    @classmethod
+    def _make_tag_generators(cls, r1, i1=None, whitelist=None) -> list:
+        """The generators in the reference's order (platform.py:974-1001), the sample barcode's first.  As
+        there, every generator reads ``r1``: with ``i1`` given, the sample barcode is cut from read 1
+        (DESIGN.md section 14)."""
+        generators = []
+        if i1:
+            generators.append(fastq.EmbeddedBarcodeGenerator(fastq_files=r1, embedded_barcodes=[cls.sample_barcode]))
+        if whitelist:
+            kwargs = {"fastq_files": r1, "whitelist": whitelist}
+            if cls.cell_barcode:
+                kwargs["embedded_cell_barcode"] = cls.cell_barcode
+            if cls.molecule_barcode:
+                kwargs["other_embedded_barcodes"] = [cls.molecule_barcode]
+            generators.append(fastq.BarcodeGeneratorWithCorrectedCellBarcodes(**kwargs))
+        else:
+            generators.append(fastq.EmbeddedBarcodeGenerator(
+                fastq_files=r1, embedded_barcodes=[b for b in (cls.cell_barcode, cls.molecule_barcode) if b]))
+        return generators
+
+    @classmethod
+    def attach_barcodes(cls, args: Iterable[str] = None) -> int:
+        parser = argparse.ArgumentParser()
+        parser.add_argument("--r1", required=True, help="FASTQ of read 1, which holds the cell and the molecule barcode")
+        parser.add_argument("--u2", required=True, help="unaligned BAM of read 2, one record per FASTQ record in the same "
+                            "order, e.g. from picard FastqToSam")
+        parser.add_argument("-o", "--output-bamfile", required=True, help="the tagged BAM to write")
+        parser.add_argument("-w", "--whitelist", default=None,
+                            help="cell barcode whitelist, one barcode per line; with it, CB is set where the raw cell "
+                                 "barcode is on the list or one substitution away from it")
+        parser.add_argument("--i1", default=None, help="FASTQ of the i7 index read; required with a sample barcode")
+        for name, where in (("sample", "sample"), ("cell", "cell"), ("molecule", "molecule")):
+            parser.add_argument("--%s-barcode-start-position" % name, dest="%s_barcode_start_pos" % name, default=None,
+                                type=cls._validate_barcode_start_pos,
+                                help="0-based position of the first base of the %s barcode" % where)
+            parser.add_argument("--%s-barcode-length" % name, dest="%s_barcode_length" % name, default=None,
+                                type=cls._validate_barcode_length,
+                                help="number of bases of the %s barcode (at least 1)" % where)
+        parser.add_argument("--device", default=None, help="GPU index or torch device (default: current GPU)")
+        args = parser.parse_args(args) if args else parser.parse_args()
+        cls._validate_barcode_args(args)
+        tags = {"cell": (consts.QUALITY_CELL_BARCODE_TAG_KEY, consts.RAW_CELL_BARCODE_TAG_KEY),
+                "molecule": (consts.QUALITY_MOLECULE_BARCODE_TAG_KEY, consts.RAW_MOLECULE_BARCODE_TAG_KEY),
+                "sample": (consts.QUALITY_SAMPLE_BARCODE_TAG_KEY, consts.RAW_SAMPLE_BARCODE_TAG_KEY)}
+        for name, (quality_tag, sequence_tag) in tags.items():
+            start, length = getattr(args, name + "_barcode_start_pos"), getattr(args, name + "_barcode_length")
+            if length:  # (set on the class and kept, as the reference does)
+                setattr(cls, name + "_barcode", fastq.EmbeddedBarcode(start=start, end=start + length,
+                                                                      quality_tag=quality_tag, sequence_tag=sequence_tag))
+        cls._tag_bamfile(args.u2, args.output_bamfile, cls._make_tag_generators(args.r1, args.i1, args.whitelist),
+                         device=args.device)
+        return 0
 
 
 COMMANDS = {
@@ -234,4 +388,6 @@ COMMANDS = {
     "CreateCountMatrix": GenericPlatform.bam_to_count_matrix,
     "MergeCountMatrices": GenericPlatform.merge_count_matrices,
     "CorrectBarcodes": GenericPlatform.correct_barcodes,
+    "Attach10xBarcodes": TenXV2.attach_barcodes,
+    "AttachBarcodes": BarcodePlatform.attach_barcodes,
 }

@@ -1,0 +1,442 @@
+"""libsct_fastq.so on the GPU: FASTQ text -> barcode columns, the generators' ``columns()`` and the
+``Attach10xBarcodes`` / ``AttachBarcodes`` commands end to end.
+
+The expectation of the kernels is :func:`expect` below, a split-and-slice in plain Python; the
+expectation of the commands is ``tests/golden/fastq/expected_tags.json.gz`` (the reference's own
+generators) and ``tests/golden/bam/test_r2_tagged.bam`` (the reference's own output).
+"""
+import ctypes
+import gzip
+import json
+import os
+import random
+
+import numpy as np
+import pytest
+
+from sctools_amd import bam, fastq, platform
+from sctools_amd.__main__ import main as cli_main
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden", "fastq")
+R1 = os.path.join(GOLD, "test_r1.fastq")
+I7 = os.path.join(GOLD, "test_i7.fastq")
+R2_BAM = os.path.join(GOLD, "test_r2.bam")
+TAGGED = os.path.join(ROOT, "tests", "golden", "bam", "test_r2_tagged.bam")
+TEST_BAM = os.path.join(ROOT, "tests", "golden", "bam", "test.bam")
+WHITELIST = os.path.join(ROOT, "tests", "golden", "barcode", "1k-august-2016.txt")
+EXPECTED = json.load(gzip.open(os.path.join(GOLD, "expected_tags.json.gz"), "rt"))
+
+TILE = fastq.TILE_BYTES
+SPANS = [(0, 16), (16, 26), (3, 4)]
+CELL, MOLECULE, SAMPLE = platform.TenXV2.cell_barcode, platform.TenXV2.molecule_barcode, platform.TenXV2.sample_barcode
+
+
+def expect(text: bytes, spans, is_last: bool):
+    """(n records, consumed, n lines, per span (sequence rows, quality rows), flags) by the record rule."""
+    lines = text.split(b"\n")
+    tail = lines.pop()  # what follows the last newline
+    if is_last and tail:
+        lines.append(tail)
+    n, max_end = len(lines) // 4, max(e for _, e in spans)
+    consumed = min(len(text), sum(len(ln) + 1 for ln in lines[:4 * n]))
+    pad = lambda ln, s, e: ln[s:e].ljust(e - s, b"\0")  # noqa: E731  (a short line leaves zero bytes)
+    cols = [([pad(lines[4 * r + 1], s, e) for r in range(n)], [pad(lines[4 * r + 3], s, e) for r in range(n)])
+            for s, e in spans]
+    flags = [(len(lines[4 * r + 1]) < max_end) | (len(lines[4 * r + 3]) < max_end) << 1
+             | (not lines[4 * r].startswith(b"@")) << 2 for r in range(n)]
+    return n, consumed, len(lines), cols, flags
+
+
+def run(text: bytes, spans, is_last: bool):
+    """The same through sct_fq_count and sct_fq_extract."""
+    import torch
+
+    lib = fastq.load()
+    dev = torch.device("cuda", 0)
+    d_text = torch.from_numpy(np.frombuffer(text + b"#" * 16, dtype=np.uint8).copy()).to(dev)  # (bytes past n_bytes are not text)
+    nbytes = ctypes.c_size_t(0)
+    fastq.check(lib.sct_fq_workspace_size(len(text), ctypes.byref(nbytes)))
+    work = torch.zeros(nbytes.value + 8, dtype=torch.uint8, device=dev)
+    result = torch.zeros(4, dtype=torch.int64, device=dev)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    fastq.check(lib.sct_fq_count(p(d_text), len(text), int(is_last), p(work), work.numel(), p(result), None))
+    n, consumed, n_lines, first = (int(x) for x in result.cpu())
+    assert first == -1
+    c_spans = (fastq.Span * len(spans))(*[fastq.Span(s, e) for s, e in spans])
+    seq = [torch.full((n, e - s), 0x55, dtype=torch.uint8, device=dev) for s, e in spans]
+    qual = [torch.full((n, e - s), 0x55, dtype=torch.uint8, device=dev) for s, e in spans]
+    flags = torch.full(((n + 3) // 4 * 4,), 0x55, dtype=torch.uint8, device=dev)
+    fastq.check(lib.sct_fq_extract(p(d_text), len(text), n, p(work), work.numel(), c_spans, len(spans),
+                                   (ctypes.c_void_p * len(spans))(*[t.data_ptr() for t in seq]),
+                                   (ctypes.c_void_p * len(spans))(*[t.data_ptr() for t in qual]),
+                                   p(flags), p(result), None))
+    torch.cuda.synchronize(dev)
+    rows = lambda t: [bytes(r) for r in t.cpu().numpy()]  # noqa: E731
+    return (n, consumed, n_lines, [(rows(a), rows(b)) for a, b in zip(seq, qual)], [int(f) for f in flags.cpu()[:n]],
+            int(result[3].cpu()))
+
+
+def check(text: bytes, spans=SPANS, is_last=True):
+    n, consumed, n_lines, cols, flags = expect(text, spans, is_last)
+    got = run(text, spans, is_last)
+    assert got[:3] == (n, consumed, n_lines)
+    assert got[4] == flags
+    assert got[5] == next((r for r, f in enumerate(flags) if f), -1)
+    for k, (want, have) in enumerate(zip(cols, got[3])):
+        assert have[0] == want[0], "sequence column of span %d" % k
+        assert have[1] == want[1], "quality column of span %d" % k
+    return n, consumed, flags
+
+
+def make_records(n, seed, name_lengths=(1, 200), first_name_length=None):
+    rng = random.Random(seed)
+    out = []
+    for r in range(n):
+        k = rng.randint(*name_lengths)
+        name = b"@" + bytes(rng.choice(b"abcdefgh:0123456789 ") for _ in range(k - 1))
+        if r == 0 and first_name_length is not None:
+            name = b"@" + b"p" * (first_name_length - 1)  # (after the draw: the other records do not depend on it)
+        seq = bytes(rng.choice(b"ACGTN") for _ in range(rng.randint(26, 30)))
+        qual = bytes(rng.randint(35, 74) for _ in seq)
+        out.append(name + b"\n" + seq + b"\n+\n" + qual + b"\n")
+    return out
+
+
+def padded(first_name_length, n=400, seed=3):
+    """Text whose first name line has ``first_name_length`` bytes (without its newline)."""
+    return b"".join(make_records(n, seed, name_lengths=(20, 60), first_name_length=first_name_length))
+
+
+def test_generated_text_through_the_c_abi():
+    text = b"".join(make_records(3000, 1))
+    assert 15 <= len(text) // TILE <= 40
+    n, consumed, flags = check(text)
+    assert n == 3000 and consumed == len(text) and not any(flags)
+    check(text, spans=[(0, 16)])
+    check(text, spans=[(0, 1), (1, 2), (2, 3), (25, 26)])
+    check(text, is_last=False)
+
+
+def offsets_of(text: bytes, what: bytes):
+    out, at = [], text.find(what)
+    while at >= 0:
+        out.append(at)
+        at = text.find(what, at + 1)
+    return out
+
+
+def shifted(kind: int, target: int):
+    """Text in which the newline that ends line ``kind`` (0 name, 1 sequence, 2 '+', 3 quality) of some
+    record is byte ``target``: the first name line is padded until it is."""
+    ends = offsets_of(padded(40), b"\n")
+    k = max(i for i, o in enumerate(ends) if i % 4 == kind and i >= 4 and o <= target)
+    text = padded(40 + target - ends[k])
+    assert offsets_of(text, b"\n")[k] == target
+    return text
+
+
+@pytest.mark.parametrize("kind", [0, 1, 2, 3])
+@pytest.mark.parametrize("target", [TILE - 1, TILE, 2 * TILE - 1, 2 * TILE])
+def test_newline_as_the_last_and_as_the_first_byte_of_a_tile(kind, target):
+    text = shifted(kind, target)
+    check(text)
+    check(text, is_last=False)
+
+
+def test_slice_straddles_a_tile_boundary():
+    for into in (1, 8, 16, 25):  # bytes of the sequence line that stay in the first tile
+        check(shifted(0, TILE - into - 1))
+    check(shifted(2, TILE - 10 - 1))  # the quality line straddles
+    check(shifted(0, 2 * TILE - 16 - 1))
+
+
+def test_name_line_of_40_kb_gives_tiles_without_a_newline():
+    text = padded(40 * 1024)
+    assert b"\n" not in text[:2 * TILE]
+    check(text)
+    recs = make_records(50, 5, name_lengths=(20, 60))
+    long_name = b"@" + b"x" * 40000 + b"\n"
+    middle = b"".join(recs[:20]) + long_name + recs[20].split(b"\n", 1)[1] + b"".join(recs[21:])
+    check(middle)
+
+
+def test_window_of_exactly_one_tile_and_one_byte_more():
+    base = padded(40, n=200)
+    for size in (TILE, TILE + 1):
+        cut = base[:size]
+        assert len(cut) == size
+        check(cut, is_last=False)
+        check(cut, is_last=True)
+        whole = padded(40 + size - len(padded(40, n=150)), n=150)  # ends with a newline on the window's last byte
+        assert len(whole) == size and whole.endswith(b"\n")
+        n, consumed, _ = check(whole)
+        assert n == 150 and consumed == size
+
+
+def test_last_line_without_a_newline():
+    text = b"".join(make_records(30, 7))[:-1]
+    n, consumed, _ = check(text, is_last=True)
+    assert n == 30 and consumed == len(text)
+    n, consumed, _ = check(text, is_last=False)  # the record is not counted: its last line may go on
+    assert n == 29 and text[consumed:].count(b"\n") == 3 and text[consumed:].startswith(b"@")
+
+
+@pytest.mark.parametrize("extra", [1, 2, 3])
+def test_trailing_lines_are_dropped_and_consumed_is_where_they_begin(extra):
+    recs = make_records(41, 8)
+    whole = b"".join(recs[:40])
+    text = whole + b"\n".join(recs[40].split(b"\n")[:extra]) + b"\n"
+    for is_last in (True, False):
+        n, consumed, _ = check(text, is_last=is_last)
+        assert n == 40 and consumed == len(whole)
+    n, consumed, _ = check(text[:-1], is_last=True)  # the dropped group's last line unterminated
+    assert n == 40 and consumed == len(whole)
+
+
+def test_zero_bytes_one_record_and_blank_lines():
+    assert check(b"")[:2] == (0, 0)
+    assert check(b"", is_last=False)[:2] == (0, 0)
+    one = make_records(1, 2)[0]
+    assert check(one)[:2] == (1, len(one))
+    assert check(one[:-1])[:2] == (1, len(one) - 1)
+    assert check(one[:-1], is_last=False)[:2] == (0, 0)
+    assert check(b"\n")[:2] == (0, 0)
+    n, _, flags = check(b"\n\n\n\n" + one + b"\n\n\n\n\n")  # blank lines count as lines
+    assert n == 3 and flags == [7, 0, 7]
+    check(b"@a\r\nACGTACGTACGTACGTACGTACGTAC\r\n+\r\nFFFFFFFFFFFFFFFFFFFFFFFFFF\r\n" * 3)  # CRLF: sliced from the line start
+
+
+def test_flags_report_the_right_records():
+    recs = make_records(900, 4, name_lengths=(20, 60))
+    parts = {r: recs[r].split(b"\n") for r in (300, 450, 600)}
+    parts[300][1] = parts[300][1][:20]  # a short sequence line
+    parts[450][0] = parts[450][0][1:]  # a name without '@'
+    parts[600][3] = parts[600][3][:5]  # a short quality line
+    for r, p in parts.items():
+        recs[r] = b"\n".join(p)
+    text = b"".join(recs)
+    assert len(text) > 4 * TILE
+    n, _, flags = check(text)
+    assert n == 900 and {r: f for r, f in enumerate(flags) if f} == {300: 1, 450: 4, 600: 2}
+    n, _, flags = check(b"".join(recs[400:]))  # another first flagged record
+    assert {r: f for r, f in enumerate(flags) if f} == {50: 4, 200: 2}
+    check(b"x" + text[1:])  # byte 0 of the window is record 0's '@'
+
+
+# ---- columns() ----
+
+def host_values(generator):
+    out = {}
+    for tags in generator:
+        for tag, value, _ in tags:
+            out.setdefault(tag, []).append(value)
+    return out
+
+
+@pytest.mark.parametrize("files", [R1, R1 + ".gz", [R1, R1]], ids=["plain", "gz", "two-files"])
+@pytest.mark.parametrize("window_bytes", [64, 1000, 16384, 1 << 20])
+def test_columns_equal_the_host_iterator(files, window_bytes):
+    gen = fastq.EmbeddedBarcodeGenerator(files, [CELL, MOLECULE])
+    want = host_values(gen)
+    windows = list(gen.columns(window_bytes=window_bytes))
+    assert all(list(w) == ["CR", "CY", "UR", "UY"] for w in windows)
+    if window_bytes == 1000:
+        assert len(windows) > 5
+    for tag in want:
+        got = [bytes(row).decode() for w in windows for row in w[tag].cpu().numpy()]
+        assert got == want[tag], tag
+        assert all(w[tag].is_cuda for w in windows)
+
+
+def test_two_files_without_a_final_newline_form_one_stream(tmp_path):
+    a, b = str(tmp_path / "a.fastq"), str(tmp_path / "b.fastq")
+    text = open(R1, "rb").read()
+    open(a, "wb").write(text[:-1])
+    open(b, "wb").write(text[:-1])
+    gen = fastq.EmbeddedBarcodeGenerator([a, b], [CELL])
+    want = host_values(gen)
+    got = [bytes(row).decode() for w in gen.columns(window_bytes=4096) for row in w["CR"].cpu().numpy()]
+    assert len(got) == 200 and got == want["CR"]
+
+
+def test_corrected_columns_equal_the_host_iterator():
+    gen = fastq.BarcodeGeneratorWithCorrectedCellBarcodes(R1, CELL, WHITELIST, [MOLECULE])
+    host = list(gen)
+    windows = list(gen.columns(window_bytes=3000))
+    assert list(windows[0]) == ["CR", "CY", "CB", "UR", "UY", "CB_index"]
+    index = np.concatenate([w["CB_index"].cpu().numpy() for w in windows])
+    cb = [bytes(r).decode() for w in windows for r in w["CB"].cpu().numpy()]
+    assert index.dtype == np.int32 and len(index) == 100
+    whitelist = [ln[:-1] for ln in open(WHITELIST)]
+    for i, tags in enumerate(host):
+        corrected = dict((t, v) for t, v, _ in tags).get("CB")
+        assert (index[i] >= 0) == (corrected is not None)
+        if corrected is not None:
+            assert cb[i] == corrected == whitelist[index[i]]
+    assert (index >= 0).any() and (index < 0).any()
+
+
+# ---- the commands ----
+
+def tags_of(path):
+    return [[(t, v) for t, v, *_ in rec.get_tags()] for rec in bam.open_alignments(path, "rb")]
+
+
+def raw_records(path):
+    """The records' bytes as they are in the file: the inflated stream after the header and the
+    reference list, cut at the block sizes."""
+    data = gzip.open(path, "rb").read()  # BGZF is a series of gzip members
+    off = 8 + int.from_bytes(data[4:8], "little")
+    n_ref = int.from_bytes(data[off:off + 4], "little")
+    off += 4
+    for _ in range(n_ref):
+        off += 8 + int.from_bytes(data[off:off + 4], "little")
+    out = []
+    while off < len(data):
+        size = int.from_bytes(data[off:off + 4], "little")
+        out.append(data[off:off + 4 + size])
+        off += 4 + size
+    return out
+
+
+def attached(plain, tag_sets):
+    """pysam's set_tag, tag by tag: an existing tag leaves its place and the new value goes last."""
+    out = dict(plain)
+    for tag, value in tag_sets:
+        out.pop(tag, None)
+        out[tag] = value
+    return list(out.items())
+
+
+@pytest.mark.parametrize("case", ["10x", "10x_whitelist"])
+def test_attach_10x_barcodes_end_to_end(case, tmp_path):
+    out = str(tmp_path / "tagged.bam")
+    args = ["Attach10xBarcodes", "--r1", R1, "--i1", I7, "--u2", R2_BAM, "-o", out]
+    if case == "10x_whitelist":
+        args += ["--whitelist", WHITELIST]
+    assert cli_main(args) == 0
+    plain, got = tags_of(R2_BAM), tags_of(out)
+    assert len(got) == 100
+    for i in range(100):
+        assert got[i] == attached(plain[i], EXPECTED[case][0][i] + EXPECTED[case][1][i]), i
+    if case == "10x_whitelist":
+        assert any("CB" in dict(t) for t in got) and not all("CB" in dict(t) for t in got)
+
+
+def test_attach_barcodes_with_a_seven_base_molecule_barcode(tmp_path):
+    out = str(tmp_path / "tagged.bam")
+    args = ["AttachBarcodes", "--r1", R1, "--i1", I7, "--u2", TEST_BAM, "--output-bamfile", out, "--whitelist", WHITELIST,
+            "--sample-barcode-start-position", "0", "--sample-barcode-length", "8",
+            "--cell-barcode-start-position", "0", "--cell-barcode-length", "16",
+            "--molecule-barcode-start-position", "16", "--molecule-barcode-length", "7"]
+    try:
+        assert cli_main(args) == 0
+    finally:
+        bp = platform.BarcodePlatform
+        bp.cell_barcode = bp.molecule_barcode = bp.sample_barcode = None
+    plain, got = tags_of(TEST_BAM), tags_of(out)
+    assert len(plain) == 606 and len(got) == 100  # the output ends with the shortest input
+    expected = EXPECTED["attach_barcodes"]
+    for i in range(100):
+        assert got[i] == attached(plain[i], expected[0][i] + expected[1][i]), i
+        assert len(dict(got[i])["UR"]) == 7
+
+
+def test_attach_barcodes_with_a_sample_barcode_only(tmp_path):
+    # no cell and no molecule barcode: the second generator has no barcode and yields empty tag sets
+    out = str(tmp_path / "tagged.bam")
+    args = ["AttachBarcodes", "--r1", R1, "--i1", I7, "--u2", R2_BAM, "-o", out,
+            "--sample-barcode-start-position", "0", "--sample-barcode-length", "8"]
+    try:
+        assert cli_main(args) == 0
+    finally:
+        bp = platform.BarcodePlatform
+        bp.cell_barcode = bp.molecule_barcode = bp.sample_barcode = None
+    plain, got = tags_of(R2_BAM), tags_of(out)
+    assert len(got) == 100
+    sample = EXPECTED["attach_barcodes"][0]  # SR/SY as the reference's generator yields them (cut from read 1)
+    for i in range(100):
+        assert got[i] == attached(plain[i], sample[i]), i
+
+
+def test_more_spans_than_one_call_takes_and_a_flag_from_the_first_group(tmp_path):
+    eb = lambda s, e, k: fastq.EmbeddedBarcode(s, e, "S%d" % k, "Q%d" % k)  # noqa: E731
+    spans = [eb(0, 26, 0), eb(0, 4, 1), eb(4, 8, 2), eb(20, 26, 3), eb(1, 2, 4), eb(2, 5, 5)]  # groups of 4 and 2
+    gen = fastq.EmbeddedBarcodeGenerator(R1, spans)
+    want = host_values(gen)
+    windows = list(gen.columns(window_bytes=5000))
+    assert list(windows[0]) == [t for k in range(6) for t in ("S%d" % k, "Q%d" % k)]
+    for tag in want:
+        assert [bytes(row).decode() for w in windows for row in w[tag].cpu().numpy()] == want[tag], tag
+    # a sequence line of 20 bytes is short for the first group (end 26) only: the second group ends at 5
+    lines = open(R1).read().splitlines(keepends=True)
+    lines[4 * 31 + 1] = lines[4 * 31 + 1][:20] + "\n"
+    r1 = str(tmp_path / "short.fastq")
+    open(r1, "w").write("".join(lines))
+    with pytest.raises(ValueError, match=r"record 31\b.*sequence line has 20 bytes.*26"):
+        list(fastq.EmbeddedBarcodeGenerator(r1, spans).columns())
+
+
+def test_tagger_with_the_eight_base_span_reproduces_the_references_bam(tmp_path):
+    out = str(tmp_path / "tagged.bam")
+    generators = [fastq.EmbeddedBarcodeGenerator(R1, [CELL, MOLECULE._replace(end=24)]),
+                  fastq.EmbeddedBarcodeGenerator(I7, [SAMPLE])]
+    bam.Tagger(R2_BAM).tag(out, generators)
+    assert raw_records(out) == raw_records(TAGGED)  # every byte of every record
+    assert tags_of(out) == tags_of(TAGGED)
+    want = list(bam.open_alignments(TAGGED, "rb"))
+    for x, y in zip(bam.open_alignments(out, "rb"), want):
+        for field in ("query_name", "flag", "reference_id", "pos", "mapq", "cigar", "l_seq", "_qual"):
+            assert getattr(x, field) == getattr(y, field), field
+
+
+def test_a_bad_record_beyond_the_bams_end_is_never_looked_at(tmp_path):
+    # the reference's zip advances a generator once more than the BAM has records and no further
+    from sctools_amd import bamnative
+
+    u2 = str(tmp_path / "forty.bam")
+    with bamnative.TagAttacher(R2_BAM, u2) as w:
+        assert w.write([], 40) == 40
+    lines = open(R1).read().splitlines(keepends=True)
+    r1, out = str(tmp_path / "bad.fastq"), str(tmp_path / "tagged.bam")
+    for bad in (41, 60):  # in the same window as the records that are written
+        edited = list(lines)
+        edited[4 * bad] = edited[4 * bad][1:]
+        edited[4 * bad + 5] = edited[4 * bad + 5][:3] + "\n"  # and a short sequence line after it
+        open(r1, "w").write("".join(edited))
+        assert cli_main(["Attach10xBarcodes", "--r1", r1, "--u2", u2, "-o", out]) == 0
+        plain, got = tags_of(u2), tags_of(out)
+        assert len(got) == 40
+        for i in range(40):
+            assert got[i] == attached(plain[i], EXPECTED["10x"][0][i]), i
+        assert [list(w) for w in fastq.EmbeddedBarcodeGenerator(r1, [CELL]).columns(max_records=bad)] == [["CR", "CY"]]
+        with pytest.raises(ValueError, match=r"record %d\b" % bad):
+            list(fastq.EmbeddedBarcodeGenerator(r1, [CELL]).columns(max_records=bad + 1))
+    edited = list(lines)
+    edited[4 * 40] = edited[4 * 40][1:]  # the record the zip still reaches: the reference raises, and so does this
+    open(r1, "w").write("".join(edited))
+    with pytest.raises(ValueError, match=r"must start with @.*record 40\b"):
+        cli_main(["Attach10xBarcodes", "--r1", r1, "--u2", u2, "-o", out])
+    assert not os.path.exists(out)
+    got = [w["CR"].shape[0] for w in fastq.EmbeddedBarcodeGenerator(R1, [CELL]).columns(window_bytes=2000, max_records=33)]
+    assert sum(got) == 33 and len(got) > 1
+
+
+def test_short_line_in_the_middle_of_r1_raises_and_leaves_no_output(tmp_path):
+    lines = open(R1).read().splitlines(keepends=True)
+    lines[4 * 57 + 1] = lines[4 * 57 + 1][:21] + "\n"
+    r1 = str(tmp_path / "short.fastq")
+    open(r1, "w").write("".join(lines))
+    out = str(tmp_path / "tagged.bam")
+    with pytest.raises(ValueError, match=r"record 57\b.*sequence line has 21 bytes.*26"):
+        cli_main(["Attach10xBarcodes", "--r1", r1, "--i1", I7, "--u2", R2_BAM, "-o", out])
+    assert not os.path.exists(out)
+    lines = open(R1).read().splitlines(keepends=True)
+    lines[4 * 12] = lines[4 * 12][1:]
+    open(r1, "w").write("".join(lines))
+    with pytest.raises(ValueError, match=r"must start with @.*record 12\b"):
+        cli_main(["Attach10xBarcodes", "--r1", r1, "--u2", R2_BAM, "-o", out])
+    assert not os.path.exists(out)
