@@ -279,36 +279,24 @@ __global__ void __launch_bounds__(kBlock) k_welford_x_ents(RecCols r, const int6
 
 // Big entities: one lane per (entity, stream) chain, kWfGroup entities x 4 streams per wave, groups
 // of similar sizes (the order is by descending log2 size), waves dequeue groups.  Every lane steps
-// the same record index k together, so RN(1 / k) is the same for all of them: the wave computes 64
-// of them at a time, one per lane in registers (one division per lane per 64 records), and record
-// q's pair reaches the chain by readlane (reading it from LDS put the LDS latency on the chain every
-// few records: 22 ms at config 2).  Per record a lane loads its sample (kWfBatch records per batch;
-// the next batch's loads, unconditional with clamped addresses, are in flight while this batch's
-// kWfBatch updates run) and runs the update: 4 dependent FP64 operations, nothing on them waiting
-// for memory or LDS.
+// the same record index k together, so RN(1 / k) is the same for all of them: every row of 16
+// lanes computes the pairs of the same 16 records, one per lane in registers (one division per lane
+// per 16 records).  Per record a lane loads its sample (kWfBatch records per batch; the next
+// batch's loads, unconditional with clamped addresses, are in flight while this batch's kWfBatch
+// updates run) and runs the update: 4 dependent FP64 operations, nothing on them waiting for memory
+// or LDS.
 constexpr int kWfGroup = kWave / 4;
 constexpr int kWfBatch = 32;
 static_assert(kWave % kWfBatch == 0, "batches tile the 64-record y chunks");
 constexpr int kWfBlocks = 2048;  // persistent grid (waves dequeue groups)
-// lane l's double, broadcast (l a compile-time constant after unrolling)
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  const uint64_t b = (uint64_t)__double_as_longlong(v);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, l);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), l);
-  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
 
-// SCT_WF_PAIRS: how record q's reciprocal pair reaches the chain lanes.  0: four v_readlane per
-// record (round 3); 1: one broadcast ds_read_b128 from a per-wave LDS row; 2 (round 4): no transfer
-// at all -- every row of 16 lanes computes the pairs of the same 16 records, and the two FP64 FMAs
-// of the division read record q's pair from lane q of their own row as a DPP operand
-// (v_fmac_f64_dpp row_newbcast:q): the lone wave that carries the longest entity is issue-bound,
-// and the readlanes were 4 of its 11 instructions per record.  t = RN(l d) is taken as
+// How record q's reciprocal pair reaches the chain lanes: no transfer at all.  The two FP64 FMAs of
+// the division read record q's pair from lane q of their own row of 16 lanes as a DPP operand
+// (v_fmac_f64_dpp row_newbcast:q).  The lone wave that carries the longest entity is issue-bound:
+// moving the pair with v_readlane cost 4 of its 11 instructions per record, and a broadcast read of
+// it from LDS put the LDS latency on the chain every few records.  t = RN(l d) is taken as
 // fma(l, d, +0), which rounds the same product once (a zero product gives +0 instead of -0 only
 // where the next fma's sum is +0 either way).
-#ifndef SCT_WF_PAIRS
-#define SCT_WF_PAIRS 2
-#endif
 #define SCT_WF_DPP_CASE(Q)                                                                                     \
   case Q:                                                                                                      \
     if (Q == 0)                                                                                                \
@@ -339,10 +327,8 @@ __global__ void __launch_bounds__(kBlock) k_welford_chains(const int64_t* __rest
                                                            WelfordCtl* __restrict__ ctl,
                                                            const double* __restrict__ xs, double* __restrict__ out_f) {
   constexpr int ns = kCell ? 4 : 3;
-  __shared__ double2 s_y_all[kWaves][kWave];
   const int lane = threadIdx.x & (kWave - 1);
   const int st = lane & 3;
-  double2* s_y = s_y_all[threadIdx.x / kWave];
   const uint32_t n_big = ctl->n_big;
   const uint32_t n_groups = (n_big + kWfGroup - 1) / kWfGroup;
   while (true) {
@@ -378,16 +364,6 @@ __global__ void __launch_bounds__(kBlock) k_welford_chains(const int64_t* __rest
 #pragma unroll
     for (int q = 0; q < kWfBatch; q++) xq[0][q] = X[4 * (q < lastx ? q : lastx)];
     for (int64_t c0 = 0; c0 < kmax; c0 += kWave) {
-      // 1 / k for this chunk's 64 record indices, as y_hi + y_lo, lane i holding k = c0 + i + 1;
-      // the chain reads record q's pair with readlane (a compile-time lane: no LDS latency on it)
-      const double kd = (double)(c0 + lane + 1);
-      const double yh = 1.0 / kd;
-      const double yl = __fma_rn(-kd, yh, 1.0) * yh;
-      if (SCT_WF_PAIRS == 1) {
-        __builtin_amdgcn_wave_barrier();  // the previous chunk's reads of the row are done (in order per wave)
-        s_y[lane] = make_double2(yh, yl);
-        __builtin_amdgcn_wave_barrier();
-      }
 #pragma unroll
       for (int hb = 0; hb < kWave / kWfBatch; hb++) {
         const int64_t c = c0 + hb * kWfBatch;
@@ -411,60 +387,32 @@ __global__ void __launch_bounds__(kBlock) k_welford_chains(const int64_t* __rest
         // waves issue in order, and after the mean add the M2 sub -> mul -> add would otherwise hold
         // the next record's ops behind two more dependent FP64 latencies (12.9 against 14.3 ms
         // at config 2, profiles/r03/s_welford_m2_pipelined/).  Same operations on the same values.
-        // SCT_WF_PAIRS 2: each row's lane j holds the pair of record c + 16 i + j for the batch's
-        // sub-chunk i of 16 records
+        // Each row's lane j holds the pair (1 / k as y_hi + y_lo) of record c + 16 i + j for the
+        // batch's sub-chunk i of 16 records
         double yh16 = 0.0, yl16 = 0.0;
         const auto update = [&](int q, bool act, bool fast) {
           const double x = xq[hb][q];
-          if (SCT_WF_PAIRS == 2) {
-            if ((q & 15) == 0) {
-              const double kq = (double)(c + q + (lane & 15) + 1);
-              yh16 = 1.0 / kq;
-              yl16 = __fma_rn(-kq, yh16, 1.0) * yh16;
-            }
-            // (no empty-asm ordering here: with the DPP FMAs the compiler's own schedule is 8 %
-            // faster, 31.0 against 33.6 ns per record, tools/debug/welford_micro.hip)
-            const double delta = x - mean;
-            const double d2 = px - mean;
-            double t = 0.0;
-            fmac_row_bcast(t, yl16, delta, q & 15);  // RN(l delta)
-            const double p2 = pdelta * d2;
-            fmac_row_bcast(t, yh16, delta, q & 15);  // RN(h delta + RN(l delta)) = RN(delta / k)
-            const double pm2 = m2 + p2;
-            m2 = fast || pact ? pm2 : m2;
-            const double nm = mean + t;
-            mean = act ? nm : mean;
-            pdelta = delta, px = x, pact = act;
-            return;
+          if ((q & 15) == 0) {
+            const double kq = (double)(c + q + (lane & 15) + 1);
+            yh16 = 1.0 / kq;
+            yl16 = __fma_rn(-kq, yh16, 1.0) * yh16;
           }
-          double h, l;
-          if (SCT_WF_PAIRS == 1) {
-            const double2 y = s_y[hb * kWfBatch + q];  // one broadcast read (every lane, one address)
-            h = y.x;
-            l = y.y;
-          } else {
-            h = readlane_f64(yh, hb * kWfBatch + q);
-            l = readlane_f64(yl, hb * kWfBatch + q);
-          }
-          // the issue order is pinned by empty asm statements (the scheduler would put the M2 ops
-          // back between two records): the two subs, the two muls, the fma and the M2 add, then
-          // the mean add
-          double delta = x - mean;
-          double d2 = px - mean;
-          asm volatile("" : "+v"(delta), "+v"(d2));
-          double t = delta * l;
-          double p2 = pdelta * d2;
-          asm volatile("" : "+v"(t), "+v"(p2));
-          double f = __fma_rn(delta, h, t);  // RN(delta / k)
-          double pm2 = m2 + p2;
-          asm volatile("" : "+v"(f), "+v"(pm2));
+          // (no empty-asm ordering here: with the DPP FMAs the compiler's own schedule is 8 %
+          // faster, 31.0 against 33.6 ns per record, tools/debug/welford_micro.hip)
+          const double delta = x - mean;
+          const double d2 = px - mean;
+          double t = 0.0;
+          fmac_row_bcast(t, yl16, delta, q & 15);  // RN(l delta)
+          const double p2 = pdelta * d2;
+          fmac_row_bcast(t, yh16, delta, q & 15);  // RN(h delta + RN(l delta)) = RN(delta / k)
+          const double pm2 = m2 + p2;
           m2 = fast || pact ? pm2 : m2;
-          const double nm = mean + f;
+          const double nm = mean + t;
           mean = act ? nm : mean;
           pdelta = delta, px = x, pact = act;
         };
-        // no lane-divergent branch around the updates: readlane must see y of every lane (a
-        // value computed under a partial exec mask would be stale in the inactive lanes)
+        // no lane-divergent branch around the updates: the DPP reads must see y of every lane of
+        // the row (a value computed under a partial exec mask would be stale in the inactive lanes)
         if (__builtin_amdgcn_ballot_w64(c + kWfBatch > clen) == 0) {  // wave-uniform
 #pragma unroll
           for (int q = 0; q < kWfBatch; q++) update(q, true, true);
@@ -537,17 +485,6 @@ static_assert(kW2InFlight <= 63, "a loader's loads in flight fit vmcnt");  // (5
 // The block barrier of k_welford_head2: LDS writes done, then s_barrier -- without the fence of
 // __syncthreads(), which also waits for every load in flight.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-#ifdef SCT_W2_PROF  // experiments (tools/debug/welford_head2_micro.hip): per-wave ticks in barriers and in all
-__device__ unsigned long long sct_w2_prof[2 * 4 + 2];
-#define W2_BARRIER()                           \
-  do {                                         \
-    const long long _t = wall_clock64();       \
-    lds_barrier();                             \
-    w2_wait += wall_clock64() - _t;            \
-  } while (0)
-#else
-#define W2_BARRIER() lds_barrier()
-#endif
 template <bool kCell>
 __global__ void __launch_bounds__(kW2Waves * kWave) k_welford_head2(const int64_t* __restrict__ ent_start,
                                                                       int64_t n_ent, int64_t n,
@@ -560,11 +497,6 @@ __global__ void __launch_bounds__(kW2Waves * kWave) k_welford_head2(const int64_
   __shared__ double s_x[kW2Slots][C][kW2Lanes];  // samples: chunk j in slot j % kW2Slots, [record][lane]
   __shared__ double s_m[2][C][kW2Lanes];         // means: chunk j in slot j & 1
   __shared__ double2 s_y[kW2Slots][C];           // the reciprocal pairs of chunk j's record indices
-#ifdef SCT_W2_PROF
-  long long w2_wait = 0;
-  const long long w2_t0 = wall_clock64();
-  const long long w2_c0 = clock64();
-#endif
   const int lane = threadIdx.x & (kWave - 1);
   const int cl = lane & (kW2Lanes - 1);  // the chain lane this lane mirrors (lanes >= kW2Lanes: copies)
   const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));  // 0 mean, 1 M2, 2-3 loaders
@@ -599,7 +531,7 @@ __global__ void __launch_bounds__(kW2Waves * kWave) k_welford_head2(const int64_
     // SIMD's registers (4 waves x 128 VGPRs each), so no wave of another kernel shares the CU.  The
     // LDS alone does not ensure it: kernels without LDS (the other chains, the fills) landed beside
     // the chain and their FP64 work delayed its operations.
-    for (int64_t p = 0; p <= P + 1; p++) W2_BARRIER();
+    for (int64_t p = 0; p <= P + 1; p++) lds_barrier();
   } else if (role >= 2) {
     // loader lane i moves 16 bytes: streams 2 (i & 1) .. +1 of entity (i / 2) % kW2Ents, at record
     // offset i / (2 kW2Ents) of the load's kW2PerLoad records (LDS row = kW2Lanes doubles)
@@ -624,15 +556,15 @@ __global__ void __launch_bounds__(kW2Waves * kWave) k_welford_head2(const int64_
     };
     for (int j = w; j < kW2Depth; j += 2) issue(j);
     if (w == 0) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(kW2After) : "memory");  // chunk 0 landed
-    W2_BARRIER();
+    lds_barrier();
     for (int64_t p = 0; p <= P; p++) {
       if ((int)(p & 1) == w) issue(p + kW2Depth);                                   // its chunk p was waited for
       else asm volatile("s_waitcnt vmcnt(%0)" : : "n"(kW2After) : "memory");  // chunk p + 1 landed
-      W2_BARRIER();
+      lds_barrier();
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no load may land in LDS after the block ends
   } else if (role == 0) {  // the mean chain, chunk p in phase p
-    W2_BARRIER();
+    lds_barrier();
     double mean = 0.0;
     for (int64_t p = 0; p < P; p++) {
       const int xs_slot = (int)(p & (kW2Slots - 1)), ms_slot = (int)(p & 1);
@@ -651,12 +583,12 @@ __global__ void __launch_bounds__(kW2Waves * kWave) k_welford_head2(const int64_
         mean = mean + qd;
         if (lane < kW2Lanes) s_m[ms_slot][q][cl] = mean;
       }
-      W2_BARRIER();
+      lds_barrier();
     }
-    W2_BARRIER();  // (phase P: the M2 wave's last chunk)
+    lds_barrier();  // (phase P: the M2 wave's last chunk)
   } else {  // the M2 terms, chunk p - 1 in phase p
-    W2_BARRIER();
-    W2_BARRIER();  // (phase 0)
+    lds_barrier();
+    lds_barrier();  // (phase 0)
     for (int64_t p = 1; p <= P; p++) {
       const int64_t c = (p - 1) * C;
       const int xs_slot = (int)((p - 1) & (kW2Slots - 1)), ms_slot = (int)((p - 1) & 1);
@@ -686,16 +618,9 @@ __global__ void __launch_bounds__(kW2Waves * kWave) k_welford_head2(const int64_
           mprev = mb[q];
         }
       }
-      W2_BARRIER();
+      lds_barrier();
     }
   }
-#ifdef SCT_W2_PROF
-  if (lane == 0 && role < kW2Work) {
-    sct_w2_prof[2 * role] = (unsigned long long)w2_wait;
-    sct_w2_prof[2 * role + 1] = (unsigned long long)(wall_clock64() - w2_t0);
-    if (role == 0) sct_w2_prof[8] = (unsigned long long)(clock64() - w2_c0);
-  }
-#endif
   if (role != 1 || !mine) return;
   double* F = out_f + e * SCT_NF;
   const int mslot = st == 0 ? SCT_F_UY_MEAN : st == 1 ? SCT_F_GQF_MEAN : st == 2 ? SCT_F_GQ_MEAN : SCT_F_CY_MEAN;

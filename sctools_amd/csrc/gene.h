@@ -584,12 +584,9 @@ __device__ __forceinline__ void gene_reduce_item(const void* __restrict__ pay, i
   const W* src = reinterpret_cast<const W*>(pay);
   W* s_sorted = reinterpret_cast<W*>(s_buf);
   const int t = threadIdx.x;
-#ifndef SCT_GENE_UYTAB
-#define SCT_GENE_UYTAB 1
-#endif
   // the work item's first payload's uy denominator (block-uniform), tabulated when < kUyTab
   const uint32_t ub0 = F::item(src[beg], g0).ub;
-  const uint32_t uy_b = (SCT_GENE_UYTAB && ub0 < (uint32_t)kUyTab) ? ub0 : kNoUyTab;
+  const uint32_t uy_b = ub0 < (uint32_t)kUyTab ? ub0 : kNoUyTab;
   if (uy_b != kNoUyTab) fill_uy_tab(uy_b, s_uytab);  // visible after the first sub-tile's barriers
   GeneAcc acc;
   acc.clear();

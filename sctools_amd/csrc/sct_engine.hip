@@ -1330,11 +1330,7 @@ int sct_tag_sort(const sct_plan_t* plan, const sct_records_t* in, const int32_t*
     uint32_t* tctl = at<uint32_t>(workspace, L.tctl);
     HIPCHK(hipMemsetAsync(tctl, 0, 2 * sizeof(uint32_t), s));
     uint32_t* pos_of = at<uint32_t>(workspace, L.recs2);  // the row buffer is free on this path
-    if (SCT_TIE_V2) {
-      LAUNCH("tag_ties", k_tie_wave2, grid, dim3(kBlock), s, keys, perm, tiebreak, n, longs, tctl);
-    } else {
-      LAUNCH("tag_ties", k_tie_wave, grid, dim3(kBlock), s, keys, perm, tiebreak, n, longs, tctl);
-    }
+    LAUNCH("tag_ties", k_tie_wave2, grid, dim3(kBlock), s, keys, perm, tiebreak, n, longs, tctl);
     uint32_t h[2] = {0, 0};
     if (int rb = readback(h, tctl, sizeof(h), s)) return rb;
     if (h[0] > 0) {  // runs longer than kTieShort: (run, tiebreak) radix sort of their records
@@ -1588,11 +1584,5 @@ int sct_finalize_partials(int32_t mode, const int64_t* partials, int64_t rows, i
          (const int64_t*)nullptr, out_ints, out_floats);
   return SCT_OK;
 }
-
-#ifdef SCT_W2_PROF  // experiments only: the Welford head kernel's per-wave barrier ticks (finalize.h)
-int sct_debug_w2_prof(unsigned long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(sct_w2_prof), sizeof(sct_w2_prof)) == hipSuccess ? 0 : -1;
-}
-#endif
 
 }  // extern "C"

@@ -394,10 +394,7 @@ __device__ __forceinline__ void fill_stream_tabs(const RecCols& r, int64_t base,
   const int tb = t / kTabU8;
   const uint32_t a = (uint32_t)(t % kTabU8);
   const uint32_t B = tb == 0 ? (uint32_t)r.uy_len[base] : (kCell ? (uint32_t)r.cy_len[base] : 0u);
-#ifndef SCT_TAB_MASK
-#define SCT_TAB_MASK 3  // experiments: which tables are used (bit 0 uy, bit 1 cy)
-#endif
-  const bool on = B < (uint32_t)kTabU8 && (kCell || tb == 0) && ((SCT_TAB_MASK >> tb) & 1);
+  const bool on = B < (uint32_t)kTabU8 && (kCell || tb == 0);
   if (a == 0) s->den[tb] = on ? B : kNoTab;
   const double x = (on && B != 0 && a <= B) ? ratio_y(a, B, 1.0 / (double)B) : 0.0;  // = ratio_rcp(a, B)
   uint32_t inc[kStreamLanes - 1];
@@ -652,10 +649,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))
     // One run across the wave's batch: the run ids of its lowest position (the lanes' previous
     // round) and its highest agree (wave-uniform LDS reads): no per-record run id or flush test.
     bool one_run = false;
-#ifndef SCT_KEY_FASTPATH
-#define SCT_KEY_FASTPATH 1
-#endif
-    if (SCT_KEY_FASTPATH && tile_n == kKTile) {  // block-uniform
+    if (tile_n == kKTile) {  // block-uniform
       const int wo = t & ~(kWave - 1) & (kBlock - 1);
       const int lo = (j0 == 0 ? 0 : (j0 - 1) * kBlock) + wo;
       const int hi = (j0 + kKeyBatch - 1) * kBlock + wo + kWave - 1;
@@ -726,13 +720,8 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))
       int64_t e = cur_e;
       if (!one_run) {
         e = valid ? ebase + (int64_t)loc_of(q, s_hb, s_wpre) : cur_e;
-#ifndef SCT_PACKED_FLUSH
-#define SCT_PACKED_FLUSH 1
-#endif
-        if (SCT_PACKED_FLUSH)  // per-lane counts <= kKItems between flushes: 16-bit fields suffice
-          wave_flush_packed16<A::kK>(acc.v, valid && e != cur_e && cur_e >= 0, cur_e, partials, slot);
-        else
-          wave_flush<A::kK>(acc.v, valid && e != cur_e && cur_e >= 0, cur_e, partials, slot);
+        // per-lane counts <= kKItems between flushes: 16-bit fields suffice
+        wave_flush_packed16<A::kK>(acc.v, valid && e != cur_e && cur_e >= 0, cur_e, partials, slot);
         if (!valid) continue;
         cur_e = e;
       }
@@ -802,10 +791,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))
       }
     }
   }
-  if (SCT_PACKED_FLUSH)
-    wave_flush_packed16<A::kK>(acc.v, cur_e >= 0, cur_e, partials, slot);
-  else
-    wave_flush<A::kK>(acc.v, cur_e >= 0, cur_e, partials, slot);
+  wave_flush_packed16<A::kK>(acc.v, cur_e >= 0, cur_e, partials, slot);
   if (kGene) {
     __syncthreads();
     // the tile's range in each present bucket: its offset inside the bucket (k_gene_emit)

@@ -354,15 +354,12 @@ __device__ __forceinline__ void tie_serial(const uint64_t* __restrict__ keys, ui
     if (i < L) perm[p + i] = (uint32_t)v[i];
 }
 
-// Round 4 (SCT_TIE_V2): runs inside the wave are sorted by odd-even transposition over their lanes
+// k_tie_wave2 (round 4): runs inside the wave are sorted by odd-even transposition over their lanes
 // (one compare-exchange round per record of the longest such run; most runs are 2-3 records, the
 // 64-lane bitonic network is kept for waves with a run longer than kTieRounds), and the run crossing
 // the wave's end is finished by the whole wave: lanes 0..kTieShort-1 load the next keys (a halo),
 // the run's records are gathered one per lane and sorted by a 16-lane bitonic network -- instead of
 // one lane walking the run with dependent loads (tie_serial, kept for runs longer than kTieShort).
-#ifndef SCT_TIE_V2
-#define SCT_TIE_V2 1
-#endif
 constexpr int kTieRounds = 8;
 
 __device__ __forceinline__ void tie_bitonic64(uint64_t& key, uint32_t& idx, int lane) {
@@ -463,51 +460,6 @@ __global__ void __launch_bounds__(kBlock) k_tie_wave2(const uint64_t* __restrict
       }
       if (mine) perm[q] = qv;
     }
-  }
-}
-
-__global__ void __launch_bounds__(kBlock) k_tie_wave(const uint64_t* __restrict__ keys, uint32_t* __restrict__ perm,
-                                                     const int32_t* __restrict__ tie, int64_t n,
-                                                     uint4* __restrict__ longs, uint32_t* __restrict__ ctl) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  const bool valid = p < n;
-  const uint64_t k = valid ? keys[p] : 0ull;
-  uint64_t kp = __shfl_up(k, 1), kn = __shfl_down(k, 1);
-  if (lane == 0) kp = (p > 0 && valid) ? keys[p - 1] : ~k;
-  if (lane == kWave - 1) kn = (p + 1 < n) ? keys[p + 1] : ~k;
-  const bool head = !valid || k != kp;
-  const bool tail = !valid || p + 1 >= n || k != kn;
-  const uint64_t H = __ballot(head), T = __ballot(tail);
-  const uint64_t upto = lane == kWave - 1 ? ~0ull : ((2ull << lane) - 1);
-  const uint64_t from = ~((1ull << lane) - 1);
-  const uint64_t hs = H & upto, ts = T & from;
-  const int s0 = hs ? 63 - __clzll((long long)hs) : -1;  // first lane of the lane's run, if in this wave
-  const int s1 = ts ? __ffsll((unsigned long long)ts) - 1 : -1;  // last lane of the run, if in this wave
-  const bool need = valid && s0 >= 0 && s1 >= 0 && s1 > s0;
-  uint32_t idx = valid ? perm[p] : 0u;
-  if (__ballot(need)) {
-    const uint32_t t = need ? (uint32_t)tie[idx] : 0u;
-    uint64_t key = ((uint64_t)(need ? s0 : lane) << 58) | ((uint64_t)t << 6) | (uint64_t)lane;
-#pragma unroll
-    for (int size = 2; size <= kWave; size <<= 1) {
-#pragma unroll
-      for (int stride = size >> 1; stride > 0; stride >>= 1) {
-        const uint64_t ok = __shfl_xor(key, stride);
-        const uint32_t ov = (uint32_t)__shfl_xor((int)idx, stride);
-        const bool asc = (lane & size) == 0 || size == kWave;
-        const bool low = (lane & stride) == 0;
-        const bool take = (low == asc) ? (ok < key) : (ok > key);
-        key = take ? ok : key;
-        idx = take ? ov : idx;
-      }
-    }
-    if (need) perm[p] = idx;
-  }
-  // the run crossing the wave's end: its first lane (in this wave) sorts all of it
-  if (!((T >> (kWave - 1)) & 1ull)) {
-    const int h = H ? 63 - __clzll((long long)H) : -1;
-    if (h >= 0 && lane == h) tie_serial(keys, perm, tie, n, p, longs, ctl);
   }
 }
 

@@ -1,6 +1,6 @@
 // Microbenchmark (experiments only): the engine's own k_welford_chains (finalize.h) on ONE entity of
 // n records (one wave, the 4 stream chains of that entity), ns per record, and the same build's
-// result bits (to compare variants).  Build variants with -D (SCT_WF_PAIRS, ...):
+// result bits (to compare variants):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I include -I sctools_amd/csrc -o wm tools/debug/welford_micro.hip
 #include <hip/hip_runtime.h>
 #include <stdio.h>
