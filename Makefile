@@ -31,7 +31,7 @@ $(GBAM): sctools_amd/csrc/gbam.hip sctools_amd/csrc/inflate.h sctools_amd/csrc/b
 $(BARCODE): sctools_amd/csrc/barcode.hip include/sct_barcode.h
 	$(HIPCC) $(HIPFLAGS) -o $@ sctools_amd/csrc/barcode.hip
 
-$(FASTQ): sctools_amd/csrc/fastq.hip include/sct_fastq.h
+$(FASTQ): sctools_amd/csrc/fastq.hip sctools_amd/csrc/fqmetrics.h include/sct_fastq.h include/sct_fastq_metrics.h
 	$(HIPCC) $(HIPFLAGS) -o $@ sctools_amd/csrc/fastq.hip
 
 $(CSVFMT): sctools_amd/csrc/csvfmt.cpp include/sct_csv.h

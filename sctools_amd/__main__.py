@@ -1,6 +1,6 @@
 """python -m sctools_amd <Command> [args]  (CalculateCellMetrics, CalculateGeneMetrics,
 MergeCellMetrics, MergeGeneMetrics, SplitBam, TagSortBam, VerifyBamSort, CreateCountMatrix,
-MergeCountMatrices, CorrectBarcodes, Attach10xBarcodes, AttachBarcodes)."""
+MergeCountMatrices, CorrectBarcodes, Attach10xBarcodes, AttachBarcodes, FastqMetrics)."""
 import sys
 
 from sctools_amd.platform import COMMANDS

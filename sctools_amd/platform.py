@@ -22,6 +22,9 @@ An addition: ``CorrectBarcodes -i BAM -o BAM --whitelist FILE [--device N]`` set
 ``CB`` from its ``CR`` and the whitelist (``ErrorsToCorrectBarcodesMap.correct_bam``,
 barcode.py:357-379), for a BAM that already carries ``CR``.
 
+From the reference's fastqpreprocessing tools: ``FastqMetrics --R1 FASTQ [--R1 FASTQ ...] --read-structure S
+--sample-id PREFIX [--white-list FILE] [--device N]`` (``fastq_metrics.cpp``; ``sctools_amd/fastq_metrics.py``).
+
 New flags are optional only: ``--float-mode {welford,exact}``, ``--device``, ``--devices N``
 (spread the entity runs over GPUs 0..N-1, one host thread each; same output) and, on
 CalculateCellMetrics, ``--gene-output-filestem STEM`` (also write the gene rows of the same
@@ -222,6 +225,27 @@ class GenericPlatform:
         corrector.correct_bam(args.input_bam, args.output_bam)
         return 0
 
+    @classmethod
+    def fastq_metrics(cls, args: Iterable[str] = None) -> int:
+        """FastqMetrics (the reference's fastqpreprocessing ``fastq_metrics`` tool): reads per cell barcode
+        and per UMI and their position weight matrices, counted on the GPU; four text files."""
+        from sctools_amd import fastq_metrics
+
+        parser = argparse.ArgumentParser(description="Reads per distinct cell barcode and UMI of R1 FASTQ files, and the "
+                                                     "base counts per barcode position")
+        parser.add_argument("--R1", action="append", required=True, help="R1 FASTQ file (plain or compressed); may be "
+                            "given several times, the files are counted together")
+        parser.add_argument("--read-structure", required=True, help="e.g. 16C10M or 8C18X6C9M1X: C cell barcode, "
+                            "M UMI, any other letter skipped")
+        parser.add_argument("--sample-id", required=True, help="prefix of the four output files")
+        parser.add_argument("--white-list", default=None, help="accepted and unused, as in the reference")
+        parser.add_argument("--device", default=None, help="GPU index or torch device (default: current GPU)")
+        args = parser.parse_args(args) if args is not None else parser.parse_args()
+        result = fastq_metrics.FastqMetrics(args.R1, args.read_structure, whitelist=args.white_list).compute(
+            device=args.device)
+        result.write(args.sample_id)
+        return 0
+
 
 class TenXV2(GenericPlatform):
     """10x Genomics v2: the metric commands (platform.py:579) and ``Attach10xBarcodes``.
@@ -390,4 +414,5 @@ COMMANDS = {
     "CorrectBarcodes": GenericPlatform.correct_barcodes,
     "Attach10xBarcodes": TenXV2.attach_barcodes,
     "AttachBarcodes": BarcodePlatform.attach_barcodes,
+    "FastqMetrics": GenericPlatform.fastq_metrics,
 }
