@@ -1,4 +1,5 @@
-# Builds the gfx950 HIP engine and the CPU oracle in-tree.
+# The one build recipe: every native library of the package, the CPU oracle and the test libraries,
+# in-tree.  __graft_entry__.build() runs the `all` target.
 HIPCC ?= /opt/rocm/bin/hipcc
 HIPFLAGS ?= --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -Wall
 ENGINE := sctools_amd/libsctools_gpu.so
@@ -28,10 +29,10 @@ $(BAMDEC): sctools_amd/csrc/bamdec.cpp sctools_amd/csrc/bamsplit.cpp sctools_amd
 $(GBAM): sctools_amd/csrc/gbam.hip sctools_amd/csrc/inflate.h sctools_amd/csrc/bgzf.h include/sct_gbam.h include/sct_bam.h
 	$(HIPCC) $(HIPFLAGS) -o $@ sctools_amd/csrc/gbam.hip -lz
 
-$(BARCODE): sctools_amd/csrc/barcode.hip include/sct_barcode.h
+$(BARCODE): sctools_amd/csrc/barcode.hip sctools_amd/csrc/liberr.h include/sct_barcode.h
 	$(HIPCC) $(HIPFLAGS) -o $@ sctools_amd/csrc/barcode.hip
 
-$(FASTQ): sctools_amd/csrc/fastq.hip sctools_amd/csrc/fqmetrics.h include/sct_fastq.h include/sct_fastq_metrics.h
+$(FASTQ): sctools_amd/csrc/fastq.hip sctools_amd/csrc/fqmetrics.h sctools_amd/csrc/liberr.h include/sct_fastq.h include/sct_fastq_metrics.h
 	$(HIPCC) $(HIPFLAGS) -o $@ sctools_amd/csrc/fastq.hip
 
 $(CSVFMT): sctools_amd/csrc/csvfmt.cpp include/sct_csv.h

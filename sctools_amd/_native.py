@@ -7,10 +7,8 @@ is missing, importing the engine raises immediately.
 """
 
 import ctypes
-import os
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("SCT_LIB_PATH") or os.path.join(HERE, "libsctools_gpu.so")  # override: experiments only
+from sctools_amd import _ffi
 
 SCT_ABI_VERSION = 2
 SCT_NI, SCT_NF, SCT_NP = 24, 12, 64
@@ -32,14 +30,6 @@ F_RPM, F_RPF, F_FPM, F_CY_VAR, F_CY_MEAN, F_PCT_MITO = 6, 7, 8, 9, 10, 11
 RECORD_COLUMNS = ("cell", "umi", "gene", "ref", "pos", "gq_sum", "gq_len", "gq_gt30", "bits", "xf",
                   "cy_gt30", "cy_len", "uy_gt30", "uy_len")
 
-EXPORTED = ("sct_abi_version", "sct_last_error", "sct_workspace_size", "sct_count_entities",
-            "sct_compute_metrics", "sct_gene_partials", "sct_cell_metrics_gene_partials",
-            "sct_finalize_partials", "sct_profile_enable", "sct_profile_only", "sct_profile_read",
-            "sct_profile_read_items",
-            "sct_tag_sort_workspace_size", "sct_tag_sort", "sct_verify_sort", "sct_count_matrix_workspace_size", "sct_count_matrix",
-            "sct_allreduce_gene_partials", "sct_comm_unique_id", "sct_comm_init_rank", "sct_comm_init_all",
-            "sct_comm_destroy", "sct_comm_abort", "sct_bin_workspace_size", "sct_bin_records", "sct_exchange_counts",
-            "sct_exchange_records")
 SCT_MAX_BINS = 256
 ORDER_CELL, ORDER_CELL_UMI_GENE, ORDER_GENE_CELL_UMI = 0, 1, 2
 PLAN_GENE_PARTIALS = 0x1
@@ -100,95 +90,53 @@ class EngineError(RuntimeError):
     """A C-ABI call returned an error code (message from sct_last_error)."""
 
 
-_lib = None
+_P = ctypes.POINTER
+_vp, _i64, _i32, _int, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int, ctypes.c_size_t
+_plan, _rec = _P(Plan), _P(Records)
+
+PROTOTYPES = {
+    "sct_abi_version": (_int, []),
+    "sct_last_error": (ctypes.c_char_p, []),
+    "sct_workspace_size": (_int, [_plan, _P(_sz)]),
+    "sct_count_entities": (_int, [_plan, _rec, _vp, _sz, _P(_i64), _vp]),
+    "sct_compute_metrics": (_int, [_plan, _rec, _vp, _vp, _vp, _sz, _vp, _vp, _i64, _P(_i64), _vp]),
+    "sct_gene_partials": (_int, [_plan, _rec, _vp, _sz, _vp, _vp]),
+    "sct_cell_metrics_gene_partials": (_int, [_plan, _rec, _vp, _vp, _sz, _vp, _vp, _i64, _P(_i64), _vp, _vp]),
+    "sct_finalize_partials": (_int, [_i32, _vp, _i64, _vp, _vp, _vp]),
+    "sct_profile_enable": (_int, [_int]),
+    "sct_profile_only": (_int, [ctypes.c_char_p]),
+    "sct_profile_read": (_int, [_P(ctypes.c_char_p), _P(ctypes.c_double), _P(_i64), _int]),
+    "sct_profile_read_items": (_int, [_P(ctypes.c_char_p), _P(ctypes.c_double), _P(_i64), _P(_i64), _int]),
+    "sct_tag_sort_workspace_size": (_int, [_plan, _P(_sz)]),
+    "sct_tag_sort": (_int, [_plan, _rec, _vp, _i32, _i32, _rec, _vp, _sz, _vp]),
+    "sct_verify_sort": (_int, [_plan, _rec, _vp, _i32, _vp, _sz, _P(_i64), _vp]),
+    "sct_count_matrix_workspace_size": (_int, [_P(CountInput), _P(_sz)]),
+    "sct_count_matrix": (_int, [_P(CountInput), _P(CountOutput), _vp, _sz, _vp]),
+    "sct_allreduce_gene_partials": (_int, [_vp, _i64, _vp, _vp]),
+    "sct_comm_unique_id": (_int, [_vp, _sz]),
+    "sct_comm_init_rank": (_int, [_P(_vp), _int, _vp, _sz, _int, _int]),
+    "sct_comm_init_all": (_int, [_P(_vp), _int, _P(_int)]),
+    "sct_comm_destroy": (_int, [_vp]),
+    "sct_comm_abort": (_int, [_vp]),
+    "sct_bin_workspace_size": (_int, [_plan, _i32, _P(_sz)]),
+    "sct_bin_records": (_int, [_plan, _rec, _vp, _vp, _i32, _rec, _vp, _vp, _vp, _sz, _vp]),
+    "sct_exchange_counts": (_int, [_vp, _vp, _i32, _vp, _vp]),
+    "sct_exchange_records": (_int, [_rec, _vp, _P(_i64), _P(_i64), _i32, _rec, _vp, _vp, _vp]),
+}
+EXPORTED = tuple(PROTOTYPES)
 
 
-def load() -> ctypes.CDLL:
-    """Load the HIP engine; raise loudly if it was not built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            "sctools_amd HIP engine not built (%s missing); run `python -c "
-            "'import __graft_entry__ as g; g.build()'`" % LIB_PATH
-        )
-    L = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
-    L.sct_abi_version.restype = ctypes.c_int
-    L.sct_abi_version.argtypes = []
-    L.sct_last_error.restype = ctypes.c_char_p
-    L.sct_last_error.argtypes = []
-    L.sct_workspace_size.restype = ctypes.c_int
-    L.sct_workspace_size.argtypes = [ctypes.POINTER(Plan), ctypes.POINTER(ctypes.c_size_t)]
-    L.sct_count_entities.restype = ctypes.c_int
-    L.sct_count_entities.argtypes = [ctypes.POINTER(Plan), ctypes.POINTER(Records), vp, ctypes.c_size_t,
-                                     ctypes.POINTER(i64), vp]
-    L.sct_compute_metrics.restype = ctypes.c_int
-    L.sct_compute_metrics.argtypes = [ctypes.POINTER(Plan), ctypes.POINTER(Records), vp, vp, vp,
-                                      ctypes.c_size_t, vp, vp, i64, ctypes.POINTER(i64), vp]
-    L.sct_gene_partials.restype = ctypes.c_int
-    L.sct_gene_partials.argtypes = [ctypes.POINTER(Plan), ctypes.POINTER(Records), vp, ctypes.c_size_t, vp, vp]
-    L.sct_cell_metrics_gene_partials.restype = ctypes.c_int
-    L.sct_cell_metrics_gene_partials.argtypes = [ctypes.POINTER(Plan), ctypes.POINTER(Records), vp, vp,
-                                                 ctypes.c_size_t, vp, vp, i64, ctypes.POINTER(i64), vp, vp]
-    L.sct_finalize_partials.restype = ctypes.c_int
-    L.sct_finalize_partials.argtypes = [i32, vp, i64, vp, vp, vp]
-    L.sct_tag_sort_workspace_size.restype = ctypes.c_int
-    L.sct_tag_sort_workspace_size.argtypes = [ctypes.POINTER(Plan), ctypes.POINTER(ctypes.c_size_t)]
-    L.sct_tag_sort.restype = ctypes.c_int
-    L.sct_tag_sort.argtypes = [ctypes.POINTER(Plan), ctypes.POINTER(Records), vp, i32, i32, ctypes.POINTER(Records),
-                               vp, ctypes.c_size_t, vp]
-    L.sct_verify_sort.restype = ctypes.c_int
-    L.sct_verify_sort.argtypes = [ctypes.POINTER(Plan), ctypes.POINTER(Records), vp, i32, vp, ctypes.c_size_t,
-                                  ctypes.POINTER(ctypes.c_int64), vp]
-    L.sct_count_matrix_workspace_size.restype = ctypes.c_int
-    L.sct_count_matrix_workspace_size.argtypes = [ctypes.POINTER(CountInput), ctypes.POINTER(ctypes.c_size_t)]
-    L.sct_count_matrix.restype = ctypes.c_int
-    L.sct_count_matrix.argtypes = [ctypes.POINTER(CountInput), ctypes.POINTER(CountOutput), vp, ctypes.c_size_t, vp]
-    L.sct_allreduce_gene_partials.restype = ctypes.c_int
-    L.sct_allreduce_gene_partials.argtypes = [vp, i64, vp, vp]
-    L.sct_comm_unique_id.restype = ctypes.c_int
-    L.sct_comm_unique_id.argtypes = [vp, ctypes.c_size_t]
-    L.sct_comm_init_rank.restype = ctypes.c_int
-    L.sct_comm_init_rank.argtypes = [ctypes.POINTER(vp), ctypes.c_int, vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int]
-    L.sct_comm_init_all.restype = ctypes.c_int
-    L.sct_comm_init_all.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
-    L.sct_comm_destroy.restype = ctypes.c_int
-    L.sct_comm_destroy.argtypes = [vp]
-    if hasattr(L, "sct_comm_abort"):
-        L.sct_comm_abort.restype = ctypes.c_int
-        L.sct_comm_abort.argtypes = [vp]
-    if hasattr(L, "sct_bin_records"):  # (an older engine given by SCT_LIB_PATH for an A/B lacks them)
-        L.sct_bin_workspace_size.restype = ctypes.c_int
-        L.sct_bin_workspace_size.argtypes = [ctypes.POINTER(Plan), i32, ctypes.POINTER(ctypes.c_size_t)]
-        L.sct_bin_records.restype = ctypes.c_int
-        L.sct_bin_records.argtypes = [ctypes.POINTER(Plan), ctypes.POINTER(Records), vp, vp, i32,
-                                      ctypes.POINTER(Records), vp, vp, vp, ctypes.c_size_t, vp]
-        L.sct_exchange_counts.restype = ctypes.c_int
-        L.sct_exchange_counts.argtypes = [vp, vp, i32, vp, vp]
-        L.sct_exchange_records.restype = ctypes.c_int
-        L.sct_exchange_records.argtypes = [ctypes.POINTER(Records), vp, ctypes.POINTER(i64), ctypes.POINTER(i64), i32,
-                                           ctypes.POINTER(Records), vp, vp, vp]
-    L.sct_profile_enable.restype = ctypes.c_int
-    L.sct_profile_enable.argtypes = [ctypes.c_int]
-    L.sct_profile_only.restype = ctypes.c_int
-    L.sct_profile_only.argtypes = [ctypes.c_char_p]
-    L.sct_profile_read.restype = ctypes.c_int
-    L.sct_profile_read.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_double),
-                                   ctypes.POINTER(i64), ctypes.c_int]
-    if hasattr(L, "sct_profile_read_items"):  # (an older engine given by SCT_LIB_PATH for an A/B lacks it)
-        L.sct_profile_read_items.restype = ctypes.c_int
-        L.sct_profile_read_items.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_double),
-                                             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
-                                             ctypes.c_int]
-    if L.sct_abi_version() != SCT_ABI_VERSION:
-        raise ImportError("libsctools_gpu.so ABI %d != %d" % (L.sct_abi_version(), SCT_ABI_VERSION))
-    _lib = L
-    return L
+def _verify_abi(lib) -> None:
+    if lib.sct_abi_version() != SCT_ABI_VERSION:
+        raise ImportError("libsctools_gpu.so ABI %d != %d" % (lib.sct_abi_version(), SCT_ABI_VERSION))
 
 
-def check(rc: int) -> None:
-    if rc != 0:
-        msg = load().sct_last_error().decode("utf-8", "replace")
-        raise EngineError("sctools_gpu error %d: %s" % (rc, msg))
+# RTLD_GLOBAL: as before this table existed.  The optional names are those an older engine given by
+# SCT_LIB_PATH for an A/B lacks.
+LIBRARY = _ffi.Library("libsctools_gpu.so", "sctools_gpu", "sct_last_error", EngineError, PROTOTYPES,
+                       env_override="SCT_LIB_PATH", mode=ctypes.RTLD_GLOBAL, verify=_verify_abi,
+                       optional=("sct_comm_abort", "sct_bin_workspace_size", "sct_bin_records", "sct_exchange_counts",
+                                 "sct_exchange_records", "sct_profile_read_items"))
+LIB_PATH = LIBRARY.path  # SCT_LIB_PATH overrides it: experiments only
+load = LIBRARY.load
+check = LIBRARY.check

@@ -549,7 +549,7 @@ def _key_columns(eng, keys, key_names, n):
     from sctools_amd import engine as E
     from sctools_amd import _native as N
 
-    cols = {c: torch.zeros(n, dtype=E._TORCH_DTYPES[c], device=eng.device) for c in N.RECORD_COLUMNS}
+    cols = {c: torch.zeros(n, dtype=E.TORCH_DTYPES[c], device=eng.device) for c in N.RECORD_COLUMNS}
     for slot, k in zip(("cell", "umi", "gene"), keys):
         cols[slot] = torch.from_numpy(np.ascontiguousarray(k, dtype=np.int32)).to(eng.device)
     size = [max(1, len(nm)) for nm in key_names] + [1] * (3 - len(key_names))

@@ -15,8 +15,7 @@ from typing import Optional
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "libsct_bam.so")
+from sctools_amd import _ffi
 
 OK, EIO, EFORMAT = 0, -1, -2
 KEYERROR, TYPEERROR, ZERODIV, VALUEERROR, EMPTY, MISSING_TAG, ETYPED = -10, -11, -12, -13, -14, -15, -16
@@ -28,79 +27,42 @@ class TypedTagValue(Exception):
     (include/sct_bam.h SCT_BAM_ETYPED)."""
 CELL_METRICS, GENE_METRICS, COUNT_MATRIX, SORT_KEYS = 0, 1, 2, 3
 _MODES = {"cell": CELL_METRICS, "gene": GENE_METRICS, "count": COUNT_MATRIX, "sortkeys": SORT_KEYS}
-EXPORTED = ("sct_bam_decode", "sct_bam_decode_tags", "sct_bam_last_error", "sct_bam_n", "sct_bam_column", "sct_bam_dictionary",
-            "sct_bam_close", "sct_bam_split", "sct_bam_write_order", "sct_bam_tag_collect", "sct_bam_tag_n",
-            "sct_bam_tag_values", "sct_bam_tag_others", "sct_bam_tag_write", "sct_bam_tag_close",
-            "sct_bam_attach_open", "sct_bam_attach_n", "sct_bam_attach_write", "sct_bam_attach_close")
 
-_lib: Optional[ctypes.CDLL] = None
+_P = ctypes.POINTER
+_vp, _i32, _i64, _int, _str = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int, ctypes.c_char_p
 
+PROTOTYPES = {
+    "sct_bam_decode": (_int, [_str, _i32, _i32, _P(_vp), _P(_i64)]),
+    "sct_bam_decode_tags": (_int, [_str, _i32, _str, _i32, _P(_vp), _P(_i64)]),
+    "sct_bam_last_error": (_str, []),
+    "sct_bam_n": (_i64, [_vp]),
+    "sct_bam_column": (_vp, [_vp, _str]),
+    "sct_bam_dictionary": (_int, [_vp, _i32, _P(_i64), _P(_vp), _P(_vp), _P(_i32)]),
+    "sct_bam_close": (None, [_vp]),
+    "sct_bam_split": (_int, [_P(_str), _i32, _str, _str, _i32, _i32, _i32, _i32, _i32, _P(_i32), _P(_i64)]),
+    "sct_bam_write_order": (_int, [_str, _str, _vp, _i64, _i32, _i32]),
+    "sct_bam_tag_collect": (_int, [_str, _str, _str, _i32, _i32, _P(_vp), _P(_i64)]),
+    "sct_bam_tag_n": (_i64, [_vp]),
+    "sct_bam_tag_values": (_vp, [_vp]),
+    "sct_bam_tag_others": (_int, [_vp, _P(_i64), _P(_vp), _P(_vp), _P(_vp)]),
+    "sct_bam_tag_write": (_int, [_vp, _str, _str, _vp, _str, _vp, _i32, _i32]),
+    "sct_bam_tag_close": (None, [_vp]),
+    "sct_bam_attach_open": (_int, [_str, _str, _i32, _i32, _P(_vp)]),
+    "sct_bam_attach_n": (_i64, [_vp]),
+    "sct_bam_attach_write": (_int, [_vp, _i64, _i32, _str, _P(_vp), _P(_i64), _P(_vp), _P(_i64)]),
+    "sct_bam_attach_close": (_int, [_vp]),
+}
+EXPORTED = tuple(PROTOTYPES)
 
-def load() -> ctypes.CDLL:
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError("%s is missing: run __graft_entry__.build() (or make)" % LIB_PATH)
-    L = ctypes.CDLL(LIB_PATH)
-    vp = ctypes.c_void_p
-    L.sct_bam_decode.restype = ctypes.c_int
-    L.sct_bam_decode.argtypes = [ctypes.c_char_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(vp),
-                                 ctypes.POINTER(ctypes.c_int64)]
-    L.sct_bam_decode_tags.restype = ctypes.c_int
-    L.sct_bam_decode_tags.argtypes = [ctypes.c_char_p, ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32,
-                                      ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64)]
-    L.sct_bam_last_error.restype = ctypes.c_char_p
-    L.sct_bam_last_error.argtypes = []
-    L.sct_bam_n.restype = ctypes.c_int64
-    L.sct_bam_n.argtypes = [vp]
-    L.sct_bam_column.restype = vp
-    L.sct_bam_column.argtypes = [vp, ctypes.c_char_p]
-    L.sct_bam_dictionary.restype = ctypes.c_int
-    L.sct_bam_dictionary.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(vp),
-                                     ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int32)]
-    L.sct_bam_close.restype = None
-    L.sct_bam_close.argtypes = [vp]
-    i32 = ctypes.c_int32
-    L.sct_bam_split.restype = ctypes.c_int
-    L.sct_bam_split.argtypes = [ctypes.POINTER(ctypes.c_char_p), i32, ctypes.c_char_p, ctypes.c_char_p, i32, i32, i32,
-                                i32, i32, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_int64)]
-    L.sct_bam_write_order.restype = ctypes.c_int
-    L.sct_bam_write_order.argtypes = [ctypes.c_char_p, ctypes.c_char_p, vp, ctypes.c_int64, i32, i32]
-    L.sct_bam_tag_collect.restype = ctypes.c_int
-    L.sct_bam_tag_collect.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, i32, i32, ctypes.POINTER(vp),
-                                      ctypes.POINTER(ctypes.c_int64)]
-    L.sct_bam_tag_n.restype = ctypes.c_int64
-    L.sct_bam_tag_n.argtypes = [vp]
-    L.sct_bam_tag_values.restype = vp
-    L.sct_bam_tag_values.argtypes = [vp]
-    L.sct_bam_tag_others.restype = ctypes.c_int
-    L.sct_bam_tag_others.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(vp), ctypes.POINTER(vp),
-                                     ctypes.POINTER(vp)]
-    L.sct_bam_tag_write.restype = ctypes.c_int
-    L.sct_bam_tag_write.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, vp, ctypes.c_char_p, vp, i32, i32]
-    L.sct_bam_tag_close.restype = None
-    L.sct_bam_tag_close.argtypes = [vp]
-    L.sct_bam_attach_open.restype = ctypes.c_int
-    L.sct_bam_attach_open.argtypes = [ctypes.c_char_p, ctypes.c_char_p, i32, i32, ctypes.POINTER(vp)]
-    L.sct_bam_attach_n.restype = ctypes.c_int64
-    L.sct_bam_attach_n.argtypes = [vp]
-    L.sct_bam_attach_write.restype = ctypes.c_int
-    L.sct_bam_attach_write.argtypes = [vp, ctypes.c_int64, i32, ctypes.c_char_p, ctypes.POINTER(vp),
-                                       ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(vp),
-                                       ctypes.POINTER(ctypes.c_int64)]
-    L.sct_bam_attach_close.restype = ctypes.c_int
-    L.sct_bam_attach_close.argtypes = [vp]
-    _lib = L
-    return L
-
-
-def available() -> bool:
-    return os.path.exists(LIB_PATH)
-
-
+# a return code is the reference's exception class for the first offending record; the message stands alone
 _EXC = {KEYERROR: KeyError, TYPEERROR: TypeError, ZERODIV: ZeroDivisionError, VALUEERROR: ValueError,
         EMPTY: RuntimeError, EFORMAT: ValueError, EIO: OSError, MISSING_TAG: RuntimeError, ETYPED: TypedTagValue}
+
+LIBRARY = _ffi.Library("libsct_bam.so", "sct_bam", "sct_bam_last_error", RuntimeError, PROTOTYPES, exceptions=_EXC)
+LIB_PATH = LIBRARY.path
+load = LIBRARY.load
+check = LIBRARY.check
+available = LIBRARY.available
 
 
 def decode(path: str, metric_mode: str = "cell", threads: int = 0, tags=("CB", "UB", "GE")):
@@ -114,7 +76,7 @@ def decode(path: str, metric_mode: str = "cell", threads: int = 0, tags=("CB", "
     three ``tags`` (a missing tag and an empty value both rank first, as "" does),
     ``arrays["qname"]`` the rank of the query name, and a fourth name list holds the query
     names in rank order."""
-    from sctools_amd.columnar import COLUMNS
+    from sctools_amd.columnar import COLUMNS, PackedDictionary
 
     L = load()
     h = ctypes.c_void_p()
@@ -124,9 +86,7 @@ def decode(path: str, metric_mode: str = "cell", threads: int = 0, tags=("CB", "
         raise ValueError("tags must be three two-character BAM tag names: %r" % (tags,))
     rc = L.sct_bam_decode_tags(os.fsencode(path), _MODES[metric_mode], tag_bytes, int(threads), ctypes.byref(h),
                                ctypes.byref(bad))
-    if rc != OK:
-        msg = L.sct_bam_last_error().decode("utf-8", "replace")
-        raise _EXC.get(rc, RuntimeError)(msg)
+    check(rc)
     try:
         n = int(L.sct_bam_n(h))
         arrays = {}
@@ -138,16 +98,7 @@ def decode(path: str, metric_mode: str = "cell", threads: int = 0, tags=("CB", "
             arrays[name] = np.frombuffer(buf, dtype=dt, count=n).copy()
         names = []
         for which in range(4 if metric_mode == "sortkeys" else 3):
-            cnt, by, off, hn = ctypes.c_int64(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int32()
-            L.sct_bam_dictionary(h, which, ctypes.byref(cnt), ctypes.byref(by), ctypes.byref(off), ctypes.byref(hn))
-            k = int(cnt.value)
-            offs = np.frombuffer((ctypes.c_int64 * (k + 1)).from_address(off.value), dtype=np.int64).copy()
-            total = int(offs[-1])
-            raw = ctypes.string_at(by.value, total) if total else b""
-            lst = [raw[offs[i]:offs[i + 1]].decode("utf-8") for i in range(k)]
-            if hn.value:
-                lst[0] = None
-            names.append(lst)
+            names.append(PackedDictionary(*_ffi.read_dictionary(L.sct_bam_dictionary, h, which)).names)
         return arrays, names
     finally:
         L.sct_bam_close(h)
@@ -166,8 +117,7 @@ def split(in_paths, out_prefix: str, tags, n_subfiles: int, raise_missing: bool 
     rc = L.sct_bam_split(arr, len(in_paths), os.fsencode(out_prefix), "".join(tags).encode(), len(tags),
                          int(n_subfiles), 1 if raise_missing else 0, int(level), int(threads), ctypes.byref(n_out),
                          ctypes.byref(bad))
-    if rc != OK:
-        raise _EXC.get(rc, RuntimeError)(L.sct_bam_last_error().decode("utf-8", "replace"))
+    check(rc)
     return int(n_out.value)
 
 
@@ -178,8 +128,7 @@ def write_order(in_path: str, out_path: str, perm, level: int = 6, threads: int 
     p = np.ascontiguousarray(perm, dtype=np.int64)
     rc = L.sct_bam_write_order(os.fsencode(in_path), os.fsencode(out_path), p.ctypes.data if p.size else None,
                                int(p.size), int(level), int(threads))
-    if rc != OK:
-        raise _EXC.get(rc, RuntimeError)(L.sct_bam_last_error().decode("utf-8", "replace"))
+    check(rc)
 
 
 class TagColumn:
@@ -195,8 +144,7 @@ class TagColumn:
         bad = ctypes.c_int64(-1)
         rc = self._lib.sct_bam_tag_collect(os.fsencode(path), src_tag.encode(), dst_tag.encode(), self.length,
                                            int(threads), ctypes.byref(self._h), ctypes.byref(bad))
-        if rc != OK:
-            raise _EXC.get(rc, RuntimeError)(self._lib.sct_bam_last_error().decode("utf-8", "replace"))
+        check(rc)
         self.n = int(self._lib.sct_bam_tag_n(self._h))
 
     def __enter__(self):
@@ -242,8 +190,7 @@ class TagColumn:
         rc = self._lib.sct_bam_tag_write(self._h, os.fsencode(out_path), self.dst_tag.encode(),
                                          v.ctypes.data if v.size else None, ob,
                                          oo.ctypes.data if oo is not None else None, int(level), int(threads))
-        if rc != OK:
-            raise _EXC.get(rc, RuntimeError)(self._lib.sct_bam_last_error().decode("utf-8", "replace"))
+        check(rc)
 
 
 class TagAttacher:
@@ -257,8 +204,7 @@ class TagAttacher:
         self.out_path = out_path
         rc = self._lib.sct_bam_attach_open(os.fsencode(in_path), os.fsencode(out_path), int(level), int(threads),
                                            ctypes.byref(self._h))
-        if rc != OK:
-            raise _EXC.get(rc, RuntimeError)(self._lib.sct_bam_last_error().decode("utf-8", "replace"))
+        check(rc)
         self.n = int(self._lib.sct_bam_attach_n(self._h))
         self.written = 0
 
@@ -303,8 +249,7 @@ class TagAttacher:
                                               for _, _, ln in keep])
         done = ctypes.c_int64(0)
         rc = self._lib.sct_bam_attach_write(self._h, n, k, names, vals, strides, lens, ctypes.byref(done))
-        if rc != OK:
-            raise _EXC.get(rc, RuntimeError)(self._lib.sct_bam_last_error().decode("utf-8", "replace"))
+        check(rc)
         self.written += int(done.value)
         return int(done.value)
 
@@ -312,8 +257,7 @@ class TagAttacher:
         if self._h:
             h, self._h = self._h, ctypes.c_void_p()
             rc = self._lib.sct_bam_attach_close(h)
-            if rc != OK:
-                raise _EXC.get(rc, RuntimeError)(self._lib.sct_bam_last_error().decode("utf-8", "replace"))
+            check(rc)
 
     def abort(self) -> None:
         """Close and remove the output."""

@@ -23,80 +23,40 @@ outside ``ACGT`` (the reference's bundled ``1k-august-2016.txt`` ends with such 
 a small host map built by the reference's rule, and an answer is the larger file index of the two.
 """
 import ctypes
-import os
 from collections import Counter
 from typing import Iterable, Iterator, Mapping, Optional
 
 import numpy as np
 
-from sctools_amd import consts
+from sctools_amd import _ffi, consts
 from sctools_amd.encodings import TwoBit
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "libsct_barcode.so")
 
 MAX_CORRECT_LENGTH = 31  # a 62-bit code leaves a value free for the table's empty slot
 MAX_PAIR_LENGTH = 32
 MAX_PAIR_BARCODES = 1 << 22
 HIST_BINS = 33
 
-EXPORTED = ("sct_bc_last_error", "sct_bc_table_size", "sct_bc_table_build", "sct_bc_correct", "sct_bc_pair_hist")
-
-_lib: Optional[ctypes.CDLL] = None
-
 
 class BarcodeError(RuntimeError):
     """A libsct_barcode.so call returned an error code (message from sct_bc_last_error)."""
 
 
-def load() -> ctypes.CDLL:
-    """Load the HIP barcode library; raise loudly if it was not built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise ImportError("sctools_amd barcode library not built (%s missing); run `python -c "
-                          "'import __graft_entry__ as g; g.build()'`" % LIB_PATH)
-    L = ctypes.CDLL(LIB_PATH)
-    vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
-    L.sct_bc_last_error.restype = ctypes.c_char_p
-    L.sct_bc_last_error.argtypes = []
-    L.sct_bc_table_size.restype = ctypes.c_int
-    L.sct_bc_table_size.argtypes = [i64, ctypes.POINTER(ctypes.c_size_t)]
-    L.sct_bc_table_build.restype = ctypes.c_int
-    L.sct_bc_table_build.argtypes = [vp, i64, i32, vp, ctypes.c_size_t, vp]
-    L.sct_bc_correct.restype = ctypes.c_int
-    L.sct_bc_correct.argtypes = [vp, i64, vp, i64, i32, vp, vp, vp]
-    L.sct_bc_pair_hist.restype = ctypes.c_int
-    L.sct_bc_pair_hist.argtypes = [vp, i64, i32, vp, vp]
-    _lib = L
-    return L
+_vp, _i64, _i32, _int, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int, ctypes.c_size_t
 
+PROTOTYPES = {
+    "sct_bc_last_error": (ctypes.c_char_p, []),
+    "sct_bc_table_size": (_int, [_i64, ctypes.POINTER(_sz)]),
+    "sct_bc_table_build": (_int, [_vp, _i64, _i32, _vp, _sz, _vp]),
+    "sct_bc_correct": (_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "sct_bc_pair_hist": (_int, [_vp, _i64, _i32, _vp, _vp]),
+}
+EXPORTED = tuple(PROTOTYPES)
 
-def check(rc: int) -> None:
-    if rc != 0:
-        raise BarcodeError("sct_barcode error %d: %s" % (rc, load().sct_bc_last_error().decode("utf-8", "replace")))
-
-
-def _device(device=None):
-    """The torch device to run on; raises when there is no GPU (engine.py: no CPU fallback)."""
-    import torch
-
-    from sctools_amd import engine
-
-    if isinstance(device, int) or (isinstance(device, str) and device.isdigit()):
-        device = torch.device("cuda", int(device))
-    return engine._device(device)
-
-
-def _stream(dev):
-    import torch
-
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+LIBRARY = _ffi.Library("libsct_barcode.so", "sct_barcode", "sct_bc_last_error", BarcodeError, PROTOTYPES)
+LIB_PATH = LIBRARY.path
+load = LIBRARY.load
+check = LIBRARY.check
+_device, _stream, _ptr = _ffi.device, _ffi.stream, _ffi.ptr
 
 
 def encode_array(raw: np.ndarray) -> np.ndarray:

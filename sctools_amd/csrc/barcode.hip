@@ -11,34 +11,12 @@
 //
 // Nothing here writes memory with anything but plain vector stores and vector atomics.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
-
-#include <string>
 
 #include "../../include/sct_barcode.h"
+#include "liberr.h"  // g_err, fail(), SCT_LIB_HIP
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
-
-#define BC_HIP(call)                                                                             \
-  do {                                                                                           \
-    hipError_t e_ = (call);                                                                      \
-    if (e_ != hipSuccess) return fail(SCT_BC_EHIP, "%s: %s", #call, hipGetErrorString(e_));      \
-  } while (0)
 
 constexpr uint64_t kEmpty = ~0ull;
 constexpr int kBlock = 256;
@@ -373,7 +351,7 @@ int sct_bc_table_build(const uint64_t* codes, int64_t n_whitelist, int32_t L, vo
   const int filter_shift = 64 - __builtin_ctzll(filter_bits);
   const uint64_t code_mask = (1ull << (2 * L)) - 1;
   const unsigned sb = (unsigned)((n_slots + kBlock - 1) / kBlock);
-  BC_HIP(hipMemsetAsync(filter, 0, filter_bits / 8, st));
+  SCT_LIB_HIP(SCT_BC_EHIP, hipMemsetAsync(filter, 0, filter_bits / 8, st));
   hipLaunchKernelGGL(bc_fill_empty, dim3(sb), dim3(kBlock), 0, st, (uint4*)table, n_slots);
   if (n_whitelist > 0) {
     const unsigned nb = (unsigned)((n_whitelist + kBlock - 1) / kBlock);
@@ -381,7 +359,7 @@ int sct_bc_table_build(const uint64_t* codes, int64_t n_whitelist, int32_t L, vo
                        filter_shift);
     hipLaunchKernelGGL(bc_finalize, dim3(sb), dim3(kBlock), 0, st, t, n_slots, Filter{filter, filter_shift}, (int)L);
   }
-  BC_HIP(hipGetLastError());
+  SCT_LIB_HIP(SCT_BC_EHIP, hipGetLastError());
   return SCT_BC_OK;
 }
 
@@ -407,7 +385,7 @@ int sct_bc_correct(const void* table, int64_t n_whitelist, const uint8_t* raw, i
   else
     hipLaunchKernelGGL(bc_correct<false>, dim3((unsigned)blocks), dim3(kBlock), 0, st, t, n_slots - 1, f, copy, raw, n, (int)L,
                        out_index, out_corrected);
-  BC_HIP(hipGetLastError());
+  SCT_LIB_HIP(SCT_BC_EHIP, hipGetLastError());
   return SCT_BC_OK;
 }
 
@@ -417,11 +395,11 @@ int sct_bc_pair_hist(const uint64_t* codes, int64_t n, int32_t L, uint64_t* hist
   if (n < 0 || n > (1ll << 22)) return fail(SCT_BC_EINVAL, "n %lld outside 0..2^22", (long long)n);
   if (!hist || (n > 0 && !codes)) return fail(SCT_BC_EINVAL, "codes or hist is NULL");
   hipStream_t st = (hipStream_t)stream;
-  BC_HIP(hipMemsetAsync(hist, 0, kBins * sizeof(uint64_t), st));
+  SCT_LIB_HIP(SCT_BC_EHIP, hipMemsetAsync(hist, 0, kBins * sizeof(uint64_t), st));
   if (n < 2) return SCT_BC_OK;
   const unsigned nt = (unsigned)((n + kTile - 1) / kTile);  // <= 4096: the grid is nt x nt blocks, never n^2
   hipLaunchKernelGGL(bc_pair_hist, dim3(nt, nt), dim3(kBlock), 0, st, codes, n, (unsigned long long*)hist);
-  BC_HIP(hipGetLastError());
+  SCT_LIB_HIP(SCT_BC_EHIP, hipGetLastError());
   return SCT_BC_OK;
 }
 

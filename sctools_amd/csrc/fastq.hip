@@ -23,34 +23,12 @@
 //
 // Nothing here writes memory with anything but plain vector stores and vector atomics.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
-
-#include <string>
 
 #include "../../include/sct_fastq.h"
+#include "liberr.h"  // g_err, fail(), SCT_LIB_HIP
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
-
-#define FQ_HIP(call)                                                                             \
-  do {                                                                                           \
-    hipError_t e_ = (call);                                                                      \
-    if (e_ != hipSuccess) return fail(SCT_FQ_EHIP, "%s: %s", #call, hipGetErrorString(e_));      \
-  } while (0)
 
 constexpr int kWave = 64;
 constexpr int kBlock = 256;
@@ -370,11 +348,11 @@ int sct_fq_count(const uint8_t* text, int64_t n_bytes, int32_t is_last, void* wo
   uint32_t* cnt = (uint32_t*)(first + (tiles > 0 ? tiles : 1));
   if (tiles > 0) {
     hipLaunchKernelGGL(k_count, dim3((unsigned)tiles), dim3(kBlock), 0, s, text, n_bytes, cnt);
-    FQ_HIP(hipGetLastError());
+    SCT_LIB_HIP(SCT_FQ_EHIP, hipGetLastError());
   }
   hipLaunchKernelGGL(k_scan, dim3(1), dim3(kScanBlock), 0, s, text, n_bytes, is_last ? 1 : 0, tiles,
                      (const uint32_t*)cnt, first, result);
-  FQ_HIP(hipGetLastError());
+  SCT_LIB_HIP(SCT_FQ_EHIP, hipGetLastError());
   return SCT_FQ_OK;
 }
 
@@ -409,12 +387,12 @@ int sct_fq_extract(const uint8_t* text, int64_t n_bytes, int64_t n_records, cons
   }
   if (n_records > 0 && (!flags || ((uintptr_t)flags & 3))) return fail(SCT_FQ_EINVAL, "flags is NULL or not 4-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  FQ_HIP(hipMemsetAsync(&result->first_flagged, 0xff, sizeof(int64_t), s));
+  SCT_LIB_HIP(SCT_FQ_EHIP, hipMemsetAsync(&result->first_flagged, 0xff, sizeof(int64_t), s));
   if (n_records == 0) return SCT_FQ_OK;
-  FQ_HIP(hipMemsetAsync(flags, 0, (size_t)((n_records + 3) & ~(int64_t)3), s));
+  SCT_LIB_HIP(SCT_FQ_EHIP, hipMemsetAsync(flags, 0, (size_t)((n_records + 3) & ~(int64_t)3), s));
   if (n_bytes == 0) return SCT_FQ_OK;  // no tile, nothing to fill
   hipLaunchKernelGGL(k_extract, dim3((unsigned)tiles_of(n_bytes)), dim3(kBlock), 0, s, a);
-  FQ_HIP(hipGetLastError());
+  SCT_LIB_HIP(SCT_FQ_EHIP, hipGetLastError());
   return SCT_FQ_OK;
 }
 

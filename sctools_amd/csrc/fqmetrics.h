@@ -1,6 +1,6 @@
 // fqmetrics.h -- the sct_fqm_* calls of libsct_fastq.so (include/sct_fastq_metrics.h): reads per
 // distinct barcode in an open-addressing table in device memory, and the per-position base
-// counts of the same column.  Included at the end of fastq.hip, whose fail() and error string it
+// counts of the same column.  Included at the end of fastq.hip, whose error state (liberr.h) it
 // shares.
 //
 //   k_fqm_accumulate  one 256-thread block per tile of 512 rows.  The tile (512 * L bytes, 16-byte
@@ -33,12 +33,6 @@
 #include "../../include/sct_fastq_metrics.h"
 
 namespace {
-
-#define FQM_HIP(call)                                                                            \
-  do {                                                                                           \
-    hipError_t e_ = (call);                                                                      \
-    if (e_ != hipSuccess) return fail(SCT_FQM_EHIP, "%s: %s", #call, hipGetErrorString(e_));     \
-  } while (0)
 
 constexpr int kFqmBlock = 256;
 constexpr int kFqmRows = SCT_FQM_TILE_ROWS;
@@ -262,7 +256,7 @@ int sct_fqm_table_init(void* table, int64_t n_slots, size_t table_bytes, void* s
   if (rc) return rc;
   hipLaunchKernelGGL(k_fqm_init, dim3((unsigned)((n_slots + kFqmBlock - 1) / kFqmBlock)), dim3(kFqmBlock), 0,
                      (hipStream_t)stream, (uint4*)table, n_slots);
-  FQM_HIP(hipGetLastError());
+  SCT_LIB_HIP(SCT_FQM_EHIP, hipGetLastError());
   return SCT_FQM_OK;
 }
 
@@ -280,12 +274,12 @@ int sct_fqm_accumulate(const uint8_t* col, int64_t n, int32_t L, void* table, in
   if (n > 0 && (!exceptions || ((uintptr_t)exceptions & 7))) return fail(SCT_FQM_EINVAL, "exceptions is NULL or not 8-byte aligned");
   if ((rc = fqm_check_result(result))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  FQM_HIP(hipMemsetAsync(&result->n_exceptions, 0, sizeof(int64_t), s));
+  SCT_LIB_HIP(SCT_FQM_EHIP, hipMemsetAsync(&result->n_exceptions, 0, sizeof(int64_t), s));
   if (n == 0) return SCT_FQM_OK;
   const int64_t tiles = (n + kFqmRows - 1) / kFqmRows;
   hipLaunchKernelGGL(k_fqm_accumulate, dim3((unsigned)tiles), dim3(kFqmBlock), 0, s, col, n, (int)L, (FqmSlot*)table,
                      (uint64_t)(n_slots - 1), (unsigned long long*)pwm, exceptions, result);
-  FQM_HIP(hipGetLastError());
+  SCT_LIB_HIP(SCT_FQM_EHIP, hipGetLastError());
   return SCT_FQM_OK;
 }
 
@@ -300,7 +294,7 @@ int sct_fqm_rehash(const void* old_table, int64_t old_slots, size_t old_bytes, v
   hipLaunchKernelGGL(k_fqm_rehash, dim3((unsigned)((old_slots + kFqmBlock - 1) / kFqmBlock)), dim3(kFqmBlock), 0,
                      (hipStream_t)stream, (const FqmSlot*)old_table, old_slots, (FqmSlot*)new_table,
                      (uint64_t)(new_slots - 1), result);
-  FQM_HIP(hipGetLastError());
+  SCT_LIB_HIP(SCT_FQM_EHIP, hipGetLastError());
   return SCT_FQM_OK;
 }
 
@@ -314,10 +308,10 @@ int sct_fqm_compact(const void* table, int64_t n_slots, size_t table_bytes, uint
     return fail(SCT_FQM_EINVAL, "keys or counts is NULL or not 8-byte aligned");
   if ((rc = fqm_check_result(result))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  FQM_HIP(hipMemsetAsync(&result->n_compacted, 0, sizeof(int64_t), s));
+  SCT_LIB_HIP(SCT_FQM_EHIP, hipMemsetAsync(&result->n_compacted, 0, sizeof(int64_t), s));
   hipLaunchKernelGGL(k_fqm_compact, dim3((unsigned)((n_slots + kFqmBlock - 1) / kFqmBlock)), dim3(kFqmBlock), 0, s,
                      (const FqmSlot*)table, n_slots, keys, counts, capacity, result);
-  FQM_HIP(hipGetLastError());
+  SCT_LIB_HIP(SCT_FQM_EHIP, hipGetLastError());
   return SCT_FQM_OK;
 }
 

@@ -7,41 +7,30 @@ The reference formats every value with ``str`` in Python and compresses with one
 ~13 s of formatting and ~34 s of gzip level 9 on one core.
 """
 import ctypes
-import os
-from typing import Optional, Sequence
+from typing import Sequence
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "libsct_csv.so")
-EXPORTED = ("sct_csv_repr_double", "sct_csv_format_rows", "sct_csv_gzip", "sct_csv_free")
+from sctools_amd import _ffi
+
 INT, FLOAT = 0, 1
 
-_lib: Optional[ctypes.CDLL] = None
+_P = ctypes.POINTER
+_vp, _i32, _i64, _int = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int
 
+PROTOTYPES = {
+    "sct_csv_repr_double": (_i32, [ctypes.c_double, ctypes.c_char_p, _i32]),
+    "sct_csv_format_rows": (_int, [_i64, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _P(_vp), _P(_i64)]),
+    "sct_csv_gzip": (_int, [_vp, _i64, _i32, _i64, _i32, _P(_vp), _P(_i64)]),
+    "sct_csv_free": (None, [_vp]),
+}
+EXPORTED = tuple(PROTOTYPES)
 
-def available() -> bool:
-    return os.path.exists(LIB_PATH)
-
-
-def load() -> ctypes.CDLL:
-    global _lib
-    if _lib is None:
-        if not available():
-            raise RuntimeError("%s is missing: run __graft_entry__.build() (or make)" % LIB_PATH)
-        L = ctypes.CDLL(LIB_PATH)
-        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-        L.sct_csv_repr_double.restype = i32
-        L.sct_csv_repr_double.argtypes = [ctypes.c_double, ctypes.c_char_p, i32]
-        L.sct_csv_format_rows.restype = ctypes.c_int
-        L.sct_csv_format_rows.argtypes = [i64, vp, vp, i32, vp, vp, vp, i32, vp, i32, i32, ctypes.POINTER(vp),
-                                          ctypes.POINTER(i64)]
-        L.sct_csv_gzip.restype = ctypes.c_int
-        L.sct_csv_gzip.argtypes = [vp, i64, i32, i64, i32, ctypes.POINTER(vp), ctypes.POINTER(i64)]
-        L.sct_csv_free.restype = None
-        L.sct_csv_free.argtypes = [vp]
-        _lib = L
-    return _lib
+# the library keeps no error text: a failed call raises with the function's name (below)
+LIBRARY = _ffi.Library("libsct_csv.so", "sct_csv", None, RuntimeError, PROTOTYPES)
+LIB_PATH = LIBRARY.path
+load = LIBRARY.load
+available = LIBRARY.available
 
 
 def repr_double(x: float) -> str:

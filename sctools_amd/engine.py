@@ -15,26 +15,22 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
+from sctools_amd import _ffi
 from sctools_amd import _native as N
 
-_TORCH_DTYPES = {
+TORCH_DTYPES = {
     "cell": torch.int32, "umi": torch.int32, "gene": torch.int32, "ref": torch.int32, "pos": torch.int32,
     "gq_sum": torch.int16, "gq_len": torch.int16, "gq_gt30": torch.int16,  # uint16 bit patterns
     "bits": torch.uint8, "xf": torch.uint8, "cy_gt30": torch.uint8, "cy_len": torch.uint8,
     "uy_gt30": torch.uint8, "uy_len": torch.uint8,
 }
+_TORCH_DTYPES = TORCH_DTYPES  # the earlier name
 
 MODES = {"cell": N.MODE_CELL, "gene": N.MODE_GENE, "gene_grouped": N.MODE_GENE_GROUPED}
 FLOAT_MODES = {"exact": N.FLOAT_EXACT_SUM, "welford": N.FLOAT_WELFORD}
 
 
-def _device(device=None) -> torch.device:
-    if not torch.cuda.is_available():
-        raise RuntimeError("sctools_amd needs a ROCm GPU (torch.cuda.is_available() is False); "
-                           "there is no CPU fallback")
-    if device is None:
-        return torch.device("cuda", torch.cuda.current_device())
-    return torch.device(device)
+_device = _ffi.device
 
 
 def to_device(arrays: Dict[str, np.ndarray], device=None) -> Dict[str, torch.Tensor]:
@@ -43,7 +39,7 @@ def to_device(arrays: Dict[str, np.ndarray], device=None) -> Dict[str, torch.Ten
     out = {}
     for c in N.RECORD_COLUMNS:
         a = np.ascontiguousarray(arrays[c])
-        t = _TORCH_DTYPES[c]
+        t = TORCH_DTYPES[c]
         if t == torch.int16:
             a = a.astype(np.uint16, copy=False).view(np.int16)
         out[c] = torch.from_numpy(a).to(dev, non_blocking=False)
@@ -60,7 +56,7 @@ def records_struct(cols: Dict[str, torch.Tensor]) -> N.Records:
             raise ValueError("column %s has %d records, expected %d" % (c, t.numel(), n))
         if not t.is_contiguous():
             raise ValueError("column %s is not contiguous" % c)
-        if t.element_size() != torch.empty((), dtype=_TORCH_DTYPES[c]).element_size():
+        if t.element_size() != torch.empty((), dtype=TORCH_DTYPES[c]).element_size():
             raise ValueError("column %s has element size %d" % (c, t.element_size()))
         setattr(r, c, t.data_ptr() if n else None)
     return r
@@ -82,9 +78,6 @@ class Engine:
         self._ws: Optional[torch.Tensor] = None
 
     # ---- helpers ----
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _plan(self, n, mode, float_mode, dims: Dims, max_entities=0, flags=0) -> N.Plan:
         p = N.Plan()
         p.flags = int(flags)
@@ -116,7 +109,7 @@ class Engine:
         ws = self.workspace(plan)
         out = ctypes.c_int64(0)
         N.check(self.lib.sct_count_entities(ctypes.byref(plan), ctypes.byref(rec), ctypes.c_void_p(ws.data_ptr()),
-                                            ws.numel(), ctypes.byref(out), self._stream()))
+                                            ws.numel(), ctypes.byref(out), _ffi.stream(self.device)))
         return int(out.value)
 
     def compute(self, cols, mode: str, dims: Dims, gene_is_mito: torch.Tensor, gene_is_multi: torch.Tensor,
@@ -137,7 +130,7 @@ class Engine:
             ctypes.byref(plan), ctypes.byref(rec), ctypes.c_void_p(gene_is_mito.data_ptr()),
             ctypes.c_void_p(gene_is_multi.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
             ctypes.c_void_p(ints.data_ptr()), ctypes.c_void_p(floats.data_ptr()), cap, ctypes.byref(rows),
-            self._stream()))
+            _ffi.stream(self.device)))
         r = int(rows.value)
         return ints[:r], floats[:r]
 
@@ -149,7 +142,7 @@ class Engine:
         if out is None:
             out = torch.empty((max(1, dims.n_gene_ids), N.SCT_NP), dtype=torch.int64, device=self.device)
         N.check(self.lib.sct_gene_partials(ctypes.byref(plan), ctypes.byref(rec), ctypes.c_void_p(ws.data_ptr()),
-                                           ws.numel(), ctypes.c_void_p(out.data_ptr()), self._stream()))
+                                           ws.numel(), ctypes.c_void_p(out.data_ptr()), _ffi.stream(self.device)))
         return out
 
     def cell_and_gene(self, cols, dims: Dims, gene_is_mito: torch.Tensor, n_entities: Optional[int] = None,
@@ -170,7 +163,7 @@ class Engine:
             ctypes.byref(plan), ctypes.byref(rec), ctypes.c_void_p(gene_is_mito.data_ptr()),
             ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.c_void_p(ints.data_ptr()),
             ctypes.c_void_p(floats.data_ptr()), cap, ctypes.byref(rows), ctypes.c_void_p(partials.data_ptr()),
-            self._stream()))
+            _ffi.stream(self.device)))
         r = int(rows.value)
         return ints[:r], floats[:r], partials
 
@@ -180,7 +173,7 @@ class Engine:
         floats = torch.empty((max(1, rows), N.SCT_NF), dtype=torch.float64, device=self.device)
         N.check(self.lib.sct_finalize_partials(MODES[mode], ctypes.c_void_p(partials.data_ptr()), rows,
                                                ctypes.c_void_p(ints.data_ptr()), ctypes.c_void_p(floats.data_ptr()),
-                                               self._stream()))
+                                               _ffi.stream(self.device)))
         return ints[:rows], floats[:rows]
 
     # ---- tag sort (TagSortBam / bam.sort_by_tags_and_queryname, bam.py:638-709) ----
@@ -204,7 +197,8 @@ class Engine:
         ws = self._sort_ws(plan)
         tb = ctypes.c_void_p(tiebreak.data_ptr()) if tiebreak is not None else None
         N.check(self.lib.sct_tag_sort(ctypes.byref(plan), ctypes.byref(rec), tb, int(n_tiebreak_ids), ORDERS[order],
-                                      ctypes.byref(orec), ctypes.c_void_p(ws.data_ptr()), ws.numel(), self._stream()))
+                                      ctypes.byref(orec), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+                                      _ffi.stream(self.device)))
         return out
 
     def verify_sort(self, cols, dims: Dims, order: str = "cell_umi_gene",
@@ -217,7 +211,7 @@ class Engine:
         out = ctypes.c_int64(0)
         N.check(self.lib.sct_verify_sort(ctypes.byref(plan), ctypes.byref(rec), tb, ORDERS[order],
                                          ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.byref(out),
-                                         self._stream()))
+                                         _ffi.stream(self.device)))
         return int(out.value)
 
     # ---- cell bins exchanged between devices (SplitBam's bins, bam.py:439-480; exchange.h) ----
@@ -240,7 +234,7 @@ class Engine:
         ptr = (lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None)
         N.check(self.lib.sct_bin_records(ctypes.byref(plan), ctypes.byref(rec), ptr(tiebreak), ptr(bin_of_cell),
                                          int(n_bins), ctypes.byref(orec), ptr(tie_out), ptr(counts),
-                                         ctypes.c_void_p(ws.data_ptr()), ws.numel(), self._stream()))
+                                         ctypes.c_void_p(ws.data_ptr()), ws.numel(), _ffi.stream(self.device)))
         return out, tie_out, counts
 
     def exchange_counts(self, counts: torch.Tensor, comm) -> torch.Tensor:
@@ -248,7 +242,7 @@ class Engine:
         [n_ranks], entry p = the records rank p sends here."""
         recv = torch.empty_like(counts)
         N.check(self.lib.sct_exchange_counts(ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(recv.data_ptr()),
-                                             int(counts.numel()), ctypes.c_void_p(comm), self._stream()))
+                                             int(counts.numel()), ctypes.c_void_p(comm), _ffi.stream(self.device)))
         return recv
 
     def exchange_records(self, binned, tiebreak, send_counts, recv_counts, comm):
@@ -257,7 +251,7 @@ class Engine:
         tiebreak or None)."""
         n_ranks = len(send_counts)
         total = int(sum(int(c) for c in recv_counts))
-        out = {c: torch.empty(total, dtype=_TORCH_DTYPES[c], device=self.device) for c in N.RECORD_COLUMNS}
+        out = {c: torch.empty(total, dtype=TORCH_DTYPES[c], device=self.device) for c in N.RECORD_COLUMNS}
         tie_out = torch.empty(total, dtype=torch.int32, device=self.device) if tiebreak is not None else None
         rec, orec = records_struct(binned), records_struct(out)
         sc = (ctypes.c_int64 * n_ranks)(*[int(c) for c in send_counts])
@@ -265,7 +259,7 @@ class Engine:
         N.check(self.lib.sct_exchange_records(
             ctypes.byref(rec), ctypes.c_void_p(tiebreak.data_ptr()) if tiebreak is not None else None, sc, rc, n_ranks,
             ctypes.byref(orec), ctypes.c_void_p(tie_out.data_ptr()) if tie_out is not None else None,
-            ctypes.c_void_p(comm), self._stream()))
+            ctypes.c_void_p(comm), _ffi.stream(self.device)))
         return out, tie_out
 
     # ---- count matrix (CountMatrix.from_sorted_tagged_bam, count.py:134-328) ----
@@ -298,7 +292,7 @@ class Engine:
         co.row_cell, co.indptr, co.indices, co.data = (row_cell.data_ptr(), indptr.data_ptr(), indices.data_ptr(),
                                                        data.data_ptr())
         N.check(self.lib.sct_count_matrix(ctypes.byref(ci), ctypes.byref(co), ctypes.c_void_p(ws.data_ptr()),
-                                          ws.numel(), self._stream()))
+                                          ws.numel(), _ffi.stream(self.device)))
         del ws
         self.count_stats = {"sorted": int(co.n_sorted), "rows": int(co.n_rows), "nnz": int(co.nnz)}
         if co.unknown_record >= 0:

@@ -8,6 +8,7 @@ with the same class names and constructors, and the barcode extraction on the GP
 ``EmbeddedBarcode``, ``extract_barcode``        a barcode's position and tags; its slices of a record
 ``EmbeddedBarcodeGenerator``                    per record, the tags of every embedded barcode
 ``BarcodeGeneratorWithCorrectedCellBarcodes``   the same, with ``CB`` where the whitelist corrects ``CR``
+``TextWindows``, ``extract_spans``              the files' text a window at a time on the GPU; its barcode columns
 
 Iterated on the host, the generators yield what the reference's yield: one list of
 ``(tag, value, "Z")`` per record.  Their device method ``columns()`` yields the same values a
@@ -26,20 +27,13 @@ from typing import Iterable, Iterator, Optional, Union
 
 import numpy as np
 
-from sctools_amd import consts, reader
+from sctools_amd import _ffi, consts, reader
 from sctools_amd.barcode import ErrorsToCorrectBarcodesMap
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "libsct_fastq.so")
 
 MAX_SPANS = 4
 TILE_BYTES = 16384
 SHORT_SEQUENCE, SHORT_QUALITY, BAD_NAME = 1, 2, 4
 INDEX_SUFFIX = "_index"  # columns()["CB_index"]: whitelist file index of CB, -1 = no correction
-
-EXPORTED = ("sct_fq_last_error", "sct_fq_workspace_size", "sct_fq_count", "sct_fq_extract")
-
-_lib: Optional[ctypes.CDLL] = None
 
 
 class FastqError(RuntimeError):
@@ -50,32 +44,21 @@ class Span(ctypes.Structure):
     _fields_ = [("start", ctypes.c_int32), ("end", ctypes.c_int32)]
 
 
-def load() -> ctypes.CDLL:
-    """Load the HIP FASTQ library; raise loudly if it was not built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise ImportError("sctools_amd fastq library not built (%s missing); run `python -c "
-                          "'import __graft_entry__ as g; g.build()'`" % LIB_PATH)
-    L = ctypes.CDLL(LIB_PATH)
-    vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
-    L.sct_fq_last_error.restype = ctypes.c_char_p
-    L.sct_fq_last_error.argtypes = []
-    L.sct_fq_workspace_size.restype = ctypes.c_int
-    L.sct_fq_workspace_size.argtypes = [i64, ctypes.POINTER(ctypes.c_size_t)]
-    L.sct_fq_count.restype = ctypes.c_int
-    L.sct_fq_count.argtypes = [vp, i64, i32, vp, ctypes.c_size_t, vp, vp]
-    L.sct_fq_extract.restype = ctypes.c_int
-    L.sct_fq_extract.argtypes = [vp, i64, i64, vp, ctypes.c_size_t, ctypes.POINTER(Span), i32, ctypes.POINTER(vp),
-                                 ctypes.POINTER(vp), vp, vp, vp]
-    _lib = L
-    return L
+_P = ctypes.POINTER
+_vp, _i64, _i32, _int, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int, ctypes.c_size_t
 
+PROTOTYPES = {
+    "sct_fq_last_error": (ctypes.c_char_p, []),
+    "sct_fq_workspace_size": (_int, [_i64, _P(_sz)]),
+    "sct_fq_count": (_int, [_vp, _i64, _i32, _vp, _sz, _vp, _vp]),
+    "sct_fq_extract": (_int, [_vp, _i64, _i64, _vp, _sz, _P(Span), _i32, _P(_vp), _P(_vp), _vp, _vp, _vp]),
+}
+EXPORTED = tuple(PROTOTYPES)
 
-def check(rc: int) -> None:
-    if rc != 0:
-        raise FastqError("sct_fastq error %d: %s" % (rc, load().sct_fq_last_error().decode("utf-8", "replace")))
+LIBRARY = _ffi.Library("libsct_fastq.so", "sct_fastq", "sct_fq_last_error", FastqError, PROTOTYPES)
+LIB_PATH = LIBRARY.path
+load = LIBRARY.load
+check = LIBRARY.check
 
 
 class Record:
@@ -248,62 +231,56 @@ class _ByteStream:
         return 0
 
 
-class _DeviceColumns:
-    """The device side shared by the two generators: text windows -> barcode columns."""
+Window = namedtuple("Window", ["text", "n_bytes", "n_records", "workspace", "host"])
 
-    def _spans(self):
-        raise NotImplementedError
 
-    def _fill(self, view, stream) -> int:
+class TextWindows:
+    """The decompressed text of ``files`` as one stream, a window of whole records at a time on the device.
+
+    Iterating yields ``Window(text, n_bytes, n_records, workspace, host)``: the device tensor whose first
+    ``n_bytes`` bytes are the window, the complete records ``sct_fq_count`` found in them, the workspace
+    it filled for ``sct_fq_extract`` (:func:`extract_spans`), and the same bytes on the host as a uint8
+    array.  What follows a window's last complete record opens the next window; a full window without
+    one whole record is doubled.  A window's tensors are overwritten when the next one is asked for.
+    """
+
+    def __init__(self, files, device=None, window_bytes: int = 256 << 20):
+        self.files = list(files)
+        self.device = _ffi.device(device)
+        stored = sum(os.stat(f).st_size for f in self.files)
+        self.cap = max(16, min(int(window_bytes), max(8 * stored + 64, 1 << 16)))
+
+    @staticmethod
+    def _fill(view, source) -> int:
         """Reads into ``view`` until it is full or the stream ends; returns the bytes read."""
         got = 0
         while got < len(view):
-            k = stream.readinto(view[got:])
+            k = source.readinto(view[got:])
             if not k:
                 break
             got += k
         return got
 
-    def _extract_windows(self, device=None, window_bytes: int = 256 << 20, max_records: Optional[int] = None):
-        """Yields ``(first record index, n, [(seq tensor, qual tensor) per span])`` per window.  With
-        ``max_records`` the stream ends after that many records and a bad record from there on is
-        never seen, as an iterator that is not advanced past its consumer's last record never sees it."""
+    def __iter__(self):
         import torch
 
-        from sctools_amd import barcode as _barcode
-
-        if self._header_comment_char is not None:
-            raise ValueError("columns() reads whole files; header_comment_char needs the host iterator")
-        spans = list(self._spans())
-        if not spans:
-            raise ValueError("no embedded barcode: there is no column to extract; iterate on the host")
-        for b in spans:
-            if not (0 <= b.start < b.end):
-                raise ValueError("barcode [%d, %d) is empty or negative" % (b.start, b.end))
-        max_end = max(b.end for b in spans)
-        lib = load()
-        dev = _barcode._device(device)
-        stored = sum(os.stat(f).st_size for f in self._files)
-        cap = max(16, min(int(window_bytes), max(8 * stored + 64, 1 << 16)))
-
-        stream = _ByteStream(self._files)
+        lib, dev, cap = load(), self.device, self.cap
+        source = _ByteStream(self.files)
         with torch.cuda.device(dev):
             host = torch.empty(cap, dtype=torch.uint8).pin_memory()
             text = torch.empty(cap, dtype=torch.uint8, device=dev)
             result = torch.empty(4, dtype=torch.int64, device=dev)
-            fill, base, eof = 0, 0, False
+            fill = 0
             while True:
                 view = host.numpy()
-                got = self._fill(view[fill:cap], stream)
-                n_bytes = fill + got
-                eof = stream.ended
+                n_bytes = fill + self._fill(view[fill:cap], source)
+                eof = source.ended
                 nbytes = ctypes.c_size_t(0)
                 check(lib.sct_fq_workspace_size(n_bytes, ctypes.byref(nbytes)))
                 work = torch.empty(int(nbytes.value) + 8, dtype=torch.uint8, device=dev)
                 text[:n_bytes].copy_(host[:n_bytes], non_blocking=True)
-                s = _barcode._stream(dev)
-                check(lib.sct_fq_count(_barcode._ptr(text), n_bytes, 1 if eof else 0, ctypes.c_void_p(work.data_ptr()),
-                                       work.numel(), ctypes.c_void_p(result.data_ptr()), s))
+                check(lib.sct_fq_count(_ffi.ptr(text), n_bytes, 1 if eof else 0, _ffi.ptr(work), work.numel(),
+                                       _ffi.ptr(result), _ffi.stream(dev)))
                 n, consumed = (int(x) for x in result[:2].cpu())
                 if n == 0:
                     if eof:
@@ -316,38 +293,7 @@ class _DeviceColumns:
                         text = torch.empty(cap, dtype=torch.uint8, device=dev)
                     fill = n_bytes
                     continue
-                columns = []
-                flags = torch.empty((n + 3) // 4 * 4, dtype=torch.uint8, device=dev)
-                all_flags, first_flagged = None, -1  # over the groups of MAX_SPANS: every call writes `flags` anew
-                for g in range(0, len(spans), MAX_SPANS):
-                    group = spans[g:g + MAX_SPANS]
-                    c_spans = (Span * len(group))(*[Span(b.start, b.end) for b in group])
-                    seq = [torch.empty((n, b.end - b.start), dtype=torch.uint8, device=dev) for b in group]
-                    qual = [torch.empty((n, b.end - b.start), dtype=torch.uint8, device=dev) for b in group]
-                    c_seq = (ctypes.c_void_p * len(group))(*[t.data_ptr() for t in seq])
-                    c_qual = (ctypes.c_void_p * len(group))(*[t.data_ptr() for t in qual])
-                    check(lib.sct_fq_extract(_barcode._ptr(text), n_bytes, n, ctypes.c_void_p(work.data_ptr()),
-                                             work.numel(), c_spans, len(group), c_seq, c_qual,
-                                             ctypes.c_void_p(flags.data_ptr()), ctypes.c_void_p(result.data_ptr()), s))
-                    columns.extend(zip(seq, qual))
-                    flagged = int(result[3].cpu())
-                    if flagged >= 0 and (first_flagged < 0 or flagged < first_flagged):
-                        first_flagged = flagged
-                    if len(spans) > MAX_SPANS:
-                        all_flags = flags.clone() if all_flags is None else all_flags | flags
-                if max_records is not None and base + n >= max_records:
-                    n, eof = max_records - base, True  # the rest of the text is nobody's business
-                    columns = [(seq[:n], qual[:n]) for seq, qual in columns]
-                    if first_flagged >= n:
-                        first_flagged = -1
-                    if n == 0:
-                        break
-                if first_flagged >= 0:
-                    # a line shorter than one group's largest end is shorter than the largest end of all
-                    flag = int((flags if all_flags is None else all_flags)[first_flagged].cpu())
-                    raise self._flag_error(view[:n_bytes], base, first_flagged, flag, max_end)
-                yield base, n, columns
-                base += n
+                yield Window(text, n_bytes, n, work, view[:n_bytes])
                 torch.cuda.current_stream(dev).synchronize()  # the copy out of `host` is done before it is refilled
                 fill = n_bytes - consumed
                 if fill:
@@ -355,16 +301,89 @@ class _DeviceColumns:
                 if eof:
                     break
 
-    @staticmethod
-    def _flag_error(window: np.ndarray, base: int, r: int, flag: int, max_end: int) -> ValueError:
-        """The ValueError of window record ``r`` (stream record ``base + r``) whose flags are ``flag``."""
-        ends = np.flatnonzero(window == 10)
-        starts = np.concatenate([[0], ends + 1])
-        stops = np.concatenate([ends, [len(window)]])
-        if flag & BAD_NAME:
-            return ValueError("FASTQ name must start with @ (record %d)" % (base + r))
-        line, which = (4 * r + 1, "sequence") if flag & SHORT_SEQUENCE else (4 * r + 3, "quality")
-        return _short_line_error(base + r, which, int(stops[line] - starts[line]), max_end)
+
+def extract_spans(window: Window, spans):
+    """The bases and qualities ``[start, end)`` of every record of ``window``, for each ``(start, end)`` of
+    ``spans``: ``([(seq, qual) per span], first_flagged, flags)`` -- uint8 ``[n_records, end - start]``
+    device tensors, the first record with a flag (-1: none) and the records' flags (``SHORT_SEQUENCE``,
+    ``SHORT_QUALITY``, ``BAD_NAME``) as a device tensor; :func:`flag_error` words them."""
+    import torch
+
+    lib = load()
+    text, n_bytes, n, work, _ = window
+    dev = text.device
+    columns = []
+    with torch.cuda.device(dev):
+        result = torch.empty(4, dtype=torch.int64, device=dev)
+        flags = torch.empty((n + 3) // 4 * 4, dtype=torch.uint8, device=dev)
+        all_flags, first_flagged = None, -1  # over the groups of MAX_SPANS: every call writes `flags` anew
+        for g in range(0, len(spans), MAX_SPANS):
+            group = spans[g:g + MAX_SPANS]
+            c_spans = (Span * len(group))(*[Span(start, end) for start, end in group])
+            seq = [torch.empty((n, end - start), dtype=torch.uint8, device=dev) for start, end in group]
+            qual = [torch.empty((n, end - start), dtype=torch.uint8, device=dev) for start, end in group]
+            c_seq = (ctypes.c_void_p * len(group))(*[t.data_ptr() for t in seq])
+            c_qual = (ctypes.c_void_p * len(group))(*[t.data_ptr() for t in qual])
+            check(lib.sct_fq_extract(_ffi.ptr(text), n_bytes, n, _ffi.ptr(work), work.numel(), c_spans, len(group),
+                                     c_seq, c_qual, _ffi.ptr(flags), _ffi.ptr(result), _ffi.stream(dev)))
+            columns.extend(zip(seq, qual))
+            flagged = int(result[3].cpu())
+            if flagged >= 0 and (first_flagged < 0 or flagged < first_flagged):
+                first_flagged = flagged
+            if len(spans) > MAX_SPANS:
+                all_flags = flags.clone() if all_flags is None else all_flags | flags
+    return columns, first_flagged, flags if all_flags is None else all_flags
+
+
+def flag_error(window: Window, base: int, r: int, flags, max_end: int) -> ValueError:
+    """The ValueError of window record ``r`` (stream record ``base + r``) that ``flags`` flags, where
+    ``max_end`` is the largest end of the spans extracted."""
+    # a line shorter than one group's largest end is shorter than the largest end of all
+    flag = int(flags[r].cpu())
+    if flag & BAD_NAME:
+        return ValueError("FASTQ name must start with @ (record %d)" % (base + r))
+    ends = np.flatnonzero(window.host == 10)
+    starts = np.concatenate([[0], ends + 1])
+    stops = np.concatenate([ends, [len(window.host)]])
+    line, which = (4 * r + 1, "sequence") if flag & SHORT_SEQUENCE else (4 * r + 3, "quality")
+    return _short_line_error(base + r, which, int(stops[line] - starts[line]), max_end)
+
+
+class _DeviceColumns:
+    """The device side shared by the two generators: text windows -> barcode columns."""
+
+    def _spans(self):
+        raise NotImplementedError
+
+    def _extract_windows(self, device=None, window_bytes: int = 256 << 20, max_records: Optional[int] = None):
+        """Yields ``(first record index, n, [(seq tensor, qual tensor) per span])`` per window.  With
+        ``max_records`` the stream ends after that many records and a bad record from there on is
+        never seen, as an iterator that is not advanced past its consumer's last record never sees it."""
+        if self._header_comment_char is not None:
+            raise ValueError("columns() reads whole files; header_comment_char needs the host iterator")
+        spans = [(b.start, b.end) for b in self._spans()]
+        if not spans:
+            raise ValueError("no embedded barcode: there is no column to extract; iterate on the host")
+        for start, end in spans:
+            if not (0 <= start < end):
+                raise ValueError("barcode [%d, %d) is empty or negative" % (start, end))
+        base = 0
+        for window in TextWindows(self._files, device, window_bytes):
+            columns, first_flagged, flags = extract_spans(window, spans)
+            n = window.n_records
+            if max_records is not None and base + n >= max_records:
+                n = max_records - base  # the rest of the text is nobody's business
+                columns = [(seq[:n], qual[:n]) for seq, qual in columns]
+                if first_flagged >= n:
+                    first_flagged = -1
+                if n == 0:
+                    break
+            if first_flagged >= 0:
+                raise flag_error(window, base, first_flagged, flags, max(end for _, end in spans))
+            yield base, n, columns
+            base += n
+            if max_records is not None and base >= max_records:
+                break
 
 
 class EmbeddedBarcodeGenerator(Reader, _DeviceColumns):

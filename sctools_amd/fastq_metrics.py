@@ -35,7 +35,7 @@ from typing import Iterable, List, Optional, Tuple, Union
 
 import numpy as np
 
-from sctools_amd import fastq
+from sctools_amd import _ffi, fastq
 
 MAX_LENGTH = 21        # SCT_FQM_MAX_LENGTH
 MIN_SLOTS = 64         # SCT_FQM_MIN_SLOTS
@@ -44,43 +44,28 @@ R = TILE_ROWS
 PWM_CLASSES = 6        # A C G T N other
 KEY_ALPHABET = b"ACGNT"  # code 0..4 of the device key: byte order
 
-EXPORTED = ("sct_fqm_last_error", "sct_fqm_table_size", "sct_fqm_table_init", "sct_fqm_accumulate", "sct_fqm_rehash",
-            "sct_fqm_compact")
-
-_lib: Optional[ctypes.CDLL] = None
-
 
 class FastqMetricsError(RuntimeError):
     """A sct_fqm_* call returned an error code (message from sct_fqm_last_error)."""
 
 
-def load() -> ctypes.CDLL:
-    """libsct_fastq.so with the sct_fqm_* prototypes set; raises loudly if it was not built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    L = fastq.load()
-    vp, i64, i32, sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_size_t
-    L.sct_fqm_last_error.restype = ctypes.c_char_p
-    L.sct_fqm_last_error.argtypes = []
-    L.sct_fqm_table_size.restype = ctypes.c_int
-    L.sct_fqm_table_size.argtypes = [i64, ctypes.POINTER(sz)]
-    L.sct_fqm_table_init.restype = ctypes.c_int
-    L.sct_fqm_table_init.argtypes = [vp, i64, sz, vp]
-    L.sct_fqm_accumulate.restype = ctypes.c_int
-    L.sct_fqm_accumulate.argtypes = [vp, i64, i32, vp, i64, sz, vp, vp, vp, vp]
-    L.sct_fqm_rehash.restype = ctypes.c_int
-    L.sct_fqm_rehash.argtypes = [vp, i64, sz, vp, i64, sz, vp, vp]
-    L.sct_fqm_compact.restype = ctypes.c_int
-    L.sct_fqm_compact.argtypes = [vp, i64, sz, vp, vp, i64, vp, vp]
-    _lib = L
-    return L
+_vp, _i64, _i32, _int, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int, ctypes.c_size_t
 
+PROTOTYPES = {
+    "sct_fqm_last_error": (ctypes.c_char_p, []),
+    "sct_fqm_table_size": (_int, [_i64, ctypes.POINTER(_sz)]),
+    "sct_fqm_table_init": (_int, [_vp, _i64, _sz, _vp]),
+    "sct_fqm_accumulate": (_int, [_vp, _i64, _i32, _vp, _i64, _sz, _vp, _vp, _vp, _vp]),
+    "sct_fqm_rehash": (_int, [_vp, _i64, _sz, _vp, _i64, _sz, _vp, _vp]),
+    "sct_fqm_compact": (_int, [_vp, _i64, _sz, _vp, _vp, _i64, _vp, _vp]),
+}
+EXPORTED = tuple(PROTOTYPES)
 
-def check(rc: int) -> None:
-    if rc != 0:
-        raise FastqMetricsError("sct_fastq_metrics error %d: %s"
-                                % (rc, load().sct_fqm_last_error().decode("utf-8", "replace")))
+# the sct_fqm_* calls live in libsct_fastq.so: fastq's handle, opened once
+LIBRARY = _ffi.Library("libsct_fastq.so", "sct_fastq_metrics", "sct_fqm_last_error", FastqMetricsError, PROTOTYPES,
+                       shares=fastq.LIBRARY)
+load = LIBRARY.load
+check = LIBRARY.check
 
 
 def parse_read_structure(read_structure: str) -> List[Tuple[str, int]]:
@@ -202,22 +187,13 @@ class _KindAccumulator:
         self.n_slots, self.table = 0, None
         self._new_table(initial_slots)
 
-    def _stream(self):
-        from sctools_amd import barcode as _barcode
-
-        return _barcode._stream(self.dev)
-
-    @staticmethod
-    def _p(t):
-        return ctypes.c_void_p(t.data_ptr())
-
     def _new_table(self, n_slots: int):
         import torch
 
         nbytes = ctypes.c_size_t(0)
         check(self.lib.sct_fqm_table_size(n_slots, ctypes.byref(nbytes)))
         table = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.dev)
-        check(self.lib.sct_fqm_table_init(self._p(table), n_slots, table.numel(), self._stream()))
+        check(self.lib.sct_fqm_table_init(_ffi.ptr(table), n_slots, table.numel(), _ffi.stream(self.dev)))
         old = (self.table, self.n_slots)
         self.table, self.n_slots = table, n_slots
         return old
@@ -240,12 +216,12 @@ class _KindAccumulator:
         want = next_slots(self.n_slots, self.distinct, n)
         if want != self.n_slots:
             old, old_slots = self._new_table(want)
-            check(self.lib.sct_fqm_rehash(self._p(old), old_slots, old.numel(), self._p(self.table), self.n_slots,
-                                          self.table.numel(), self._p(self.result), self._stream()))
+            check(self.lib.sct_fqm_rehash(_ffi.ptr(old), old_slots, old.numel(), _ffi.ptr(self.table), self.n_slots,
+                                          self.table.numel(), _ffi.ptr(self.result), _ffi.stream(self.dev)))
         exceptions = torch.empty(n, dtype=torch.int64, device=self.dev)
-        check(self.lib.sct_fqm_accumulate(self._p(col), n, self.length, self._p(self.table), self.n_slots,
-                                          self.table.numel(), self._p(self.pwm), self._p(exceptions),
-                                          self._p(self.result), self._stream()))
+        check(self.lib.sct_fqm_accumulate(_ffi.ptr(col), n, self.length, _ffi.ptr(self.table), self.n_slots,
+                                          self.table.numel(), _ffi.ptr(self.pwm), _ffi.ptr(exceptions),
+                                          _ffi.ptr(self.result), _ffi.stream(self.dev)))
         n_exceptions, _ = self._read_result()  # (waits for the kernels: `old` and `col` are free from here)
         if n_exceptions:
             rows = col[exceptions[:n_exceptions]].cpu().numpy()
@@ -258,8 +234,8 @@ class _KindAccumulator:
 
         keys = torch.empty(max(self.distinct, 1), dtype=torch.int64, device=self.dev)
         counts = torch.empty(max(self.distinct, 1), dtype=torch.int64, device=self.dev)
-        check(self.lib.sct_fqm_compact(self._p(self.table), self.n_slots, self.table.numel(), self._p(keys),
-                                       self._p(counts), self.distinct, self._p(self.result), self._stream()))
+        check(self.lib.sct_fqm_compact(_ffi.ptr(self.table), self.n_slots, self.table.numel(), _ffi.ptr(keys),
+                                       _ffi.ptr(counts), self.distinct, _ffi.ptr(self.result), _ffi.stream(self.dev)))
         _, compacted = self._read_result()
         if compacted != self.distinct:
             raise FastqMetricsError("%d occupied slots, %d distinct keys counted" % (compacted, self.distinct))
@@ -309,22 +285,22 @@ class FastqMetrics:
         by the growth rule of ``include/sct_fastq_metrics.h``."""
         import torch
 
-        from sctools_amd import barcode as _barcode
-
         spans = self.barcode_spans + self.umi_spans
-        generator = fastq.EmbeddedBarcodeGenerator(
-            self.r1_files, [fastq.EmbeddedBarcode(start=s, end=e, sequence_tag="s%d" % i, quality_tag="q%d" % i)
-                            for i, (s, e) in enumerate(spans)], mode="rb")
-        dev = _barcode._device(device)
+        max_end = max(end for _, end in spans)
         slots = MIN_SLOTS
         while slots < int(initial_slots):
             slots *= 2
+        windows = fastq.TextWindows(self.r1_files, device, window_bytes)
+        dev = windows.device
         n_records = 0
         with torch.cuda.device(dev):
             kinds = [_KindAccumulator(length, slots, dev) if length else None
                      for length in (self.barcode_length, self.umi_length)]
-            for _, n, cols in generator._extract_windows(device=dev, window_bytes=window_bytes):
-                n_records += n
+            for window in windows:
+                cols, first_flagged, flags = fastq.extract_spans(window, spans)
+                if first_flagged >= 0:
+                    raise fastq.flag_error(window, n_records, first_flagged, flags, max_end)
+                n_records += window.n_records
                 seqs = [seq for seq, _ in cols]
                 groups = (seqs[:len(self.barcode_spans)], seqs[len(self.barcode_spans):])
                 for kind, group in zip(kinds, groups):

@@ -19,90 +19,59 @@ from typing import Optional
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("SCT_GBAM_LIB_PATH") or os.path.join(HERE, "libsct_gbam.so")  # override: experiments only
+from sctools_amd import _ffi
 
 OK, HOST = 0, 1
 _MODES = {"cell": 0, "gene": 1}
-EXPORTED = ("sct_gbam_open", "sct_gbam_open_part", "sct_gbam_part_bounds", "sct_gbam_merge_dictionaries",
-            "sct_gbam_remap", "sct_gbam_parse", "sct_gbam_parse_count", "sct_gbam_dictionary", "sct_gbam_read_inflated",
-            "sct_gbam_timing", "sct_gbam_windows", "sct_gbam_close", "sct_gbam_last_error")
 STAGES = ("map_scan", "h2d", "inflate", "record_starts", "parse_intern", "dictionaries", "members",
           "start_rounds")
 
-_lib: Optional[ctypes.CDLL] = None
+_P = ctypes.POINTER
+_vp, _i32, _i64, _u64, _int = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int
 
+PROTOTYPES = {
+    "sct_gbam_open": (_int, [ctypes.c_char_p, _i32, _vp, _P(_vp), _P(_i64)]),
+    "sct_gbam_open_part": (_int, [ctypes.c_char_p, _i32, _i32, _i64, _i32, _vp, _P(_vp), _P(_i64)]),
+    "sct_gbam_part_bounds": (_int, [_vp, _P(_i64), _P(_i64)]),
+    "sct_gbam_merge_dictionaries": (_int, [_P(_vp), _i32, _i32, _P(_P(_i32))]),
+    "sct_gbam_remap": (_int, [_vp, _P(_i32), _i64, _vp, _i64]),
+    "sct_gbam_parse": (_int, [_vp, _i32, _P(_vp)]),
+    "sct_gbam_parse_count": (_int, [_vp, ctypes.c_char_p, _P(_vp)]),
+    "sct_gbam_dictionary": (_int, [_vp, _i32, _P(_i64), _P(_vp), _P(_vp), _P(_i32)]),
+    "sct_gbam_read_inflated": (_int, [_vp, _u64, _u64, _vp, _P(_u64)]),
+    "sct_gbam_timing": (_int, [_vp, _P(ctypes.c_double)]),
+    "sct_gbam_windows": (_i64, [_vp]),
+    "sct_gbam_close": (None, [_vp]),
+    "sct_gbam_last_error": (ctypes.c_char_p, []),
+}
+EXPORTED = tuple(PROTOTYPES)
 
-def available() -> bool:
-    return os.path.exists(LIB_PATH)
-
-
-def load() -> ctypes.CDLL:
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not available():
-        raise RuntimeError("%s is missing: run __graft_entry__.build() (or make)" % LIB_PATH)
-    L = ctypes.CDLL(LIB_PATH)
-    vp, i32, i64, u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
-    L.sct_gbam_open.restype = ctypes.c_int
-    L.sct_gbam_open.argtypes = [ctypes.c_char_p, i32, vp, ctypes.POINTER(vp), ctypes.POINTER(i64)]
-    L.sct_gbam_open_part.restype = ctypes.c_int
-    L.sct_gbam_open_part.argtypes = [ctypes.c_char_p, i32, i32, i64, i32, vp, ctypes.POINTER(vp), ctypes.POINTER(i64)]
-    L.sct_gbam_part_bounds.restype = ctypes.c_int
-    L.sct_gbam_part_bounds.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]
-    L.sct_gbam_merge_dictionaries.restype = ctypes.c_int
-    L.sct_gbam_merge_dictionaries.argtypes = [ctypes.POINTER(vp), i32, i32, ctypes.POINTER(ctypes.POINTER(i32))]
-    L.sct_gbam_remap.restype = ctypes.c_int
-    L.sct_gbam_remap.argtypes = [vp, ctypes.POINTER(i32), i64, vp, i64]
-    L.sct_gbam_parse.restype = ctypes.c_int
-    L.sct_gbam_parse.argtypes = [vp, i32, ctypes.POINTER(vp)]
-    L.sct_gbam_parse_count.restype = ctypes.c_int
-    L.sct_gbam_parse_count.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp)]
-    L.sct_gbam_dictionary.restype = ctypes.c_int
-    L.sct_gbam_dictionary.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(vp), ctypes.POINTER(vp),
-                                      ctypes.POINTER(i32)]
-    L.sct_gbam_read_inflated.restype = ctypes.c_int
-    L.sct_gbam_read_inflated.argtypes = [vp, u64, u64, vp, ctypes.POINTER(u64)]
-    L.sct_gbam_timing.restype = ctypes.c_int
-    L.sct_gbam_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
-    L.sct_gbam_windows.restype = ctypes.c_int64
-    L.sct_gbam_windows.argtypes = [vp]
-    L.sct_gbam_close.restype = None
-    L.sct_gbam_close.argtypes = [vp]
-    L.sct_gbam_last_error.restype = ctypes.c_char_p
-    L.sct_gbam_last_error.argtypes = []
-    _lib = L
-    return L
-
-
-def last_error() -> str:
-    return load().sct_gbam_last_error().decode("utf-8", "replace")
-
-
-def _device(device):
-    import torch
-
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    if dev.index is None:  # "cuda": the current device, for the library and the stream alike
-        dev = torch.device("cuda", torch.cuda.current_device())
-    return dev
+# HOST is no error: the file goes to the host decoder
+LIBRARY = _ffi.Library("libsct_gbam.so", "device BAM decode failed", "sct_gbam_last_error", OSError, PROTOTYPES,
+                       env_override="SCT_GBAM_LIB_PATH", accept=(OK, HOST), error_format="%s (%d): %s")
+LIB_PATH = LIBRARY.path  # SCT_GBAM_LIB_PATH overrides it: experiments only
+load = LIBRARY.load
+available = LIBRARY.available
+last_error = LIBRARY.last_error
+_check = LIBRARY.check
+_device = _ffi.device
 
 
 class _Handle:
     def __init__(self, path: str, device, part: int = 0, n_parts: int = 1, first_start: int = -1):
-        import torch
-
         self.L = load()
         self.dev = _device(device)
-        self.stream = torch.cuda.current_stream(self.dev)
         self.h = ctypes.c_void_p()
         n = ctypes.c_int64(0)
         self.rc = self.L.sct_gbam_open_part(os.fsencode(path), int(part), int(n_parts), int(first_start),
-                                            int(self.dev.index), ctypes.c_void_p(self.stream.cuda_stream),
+                                            int(self.dev.index), _ffi.stream(self.dev),
                                             ctypes.byref(self.h), ctypes.byref(n))
         self.err = last_error()  # (thread-local in the library: read on the calling thread)
         self.n = int(n.value)
+
+    def check_open(self):
+        """Raises what the open returned, with the message read on the thread that opened."""
+        _check(self.rc, self.err)
 
     def bounds(self):
         a, b = ctypes.c_int64(), ctypes.c_int64()
@@ -111,30 +80,13 @@ class _Handle:
 
     def dictionary_size(self, which: int) -> int:
         """Entries of dictionary ``which`` (the count alone: no copy of its strings)."""
-        cnt, by, off, hn = ctypes.c_int64(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int32()
-        self.L.sct_gbam_dictionary(self.h, which, ctypes.byref(cnt), ctypes.byref(by), ctypes.byref(off),
-                                   ctypes.byref(hn))
-        return int(cnt.value)
+        return len(_ffi.read_dictionary(self.L.sct_gbam_dictionary, self.h, which, strings=False)[1]) - 1
 
     def dictionary(self, which: int, lazy: bool = True):
-        cnt, by, off, hn = ctypes.c_int64(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int32()
-        self.L.sct_gbam_dictionary(self.h, which, ctypes.byref(cnt), ctypes.byref(by), ctypes.byref(off),
-                                   ctypes.byref(hn))
-        k = int(cnt.value)
-        if k == 0 or not off.value:
-            offs = np.zeros(1, dtype=np.int64)
-        else:
-            offs = np.frombuffer((ctypes.c_int64 * (k + 1)).from_address(off.value), dtype=np.int64).copy()
-        total = int(offs[-1])
-        raw = ctypes.string_at(by.value, total) if total else b""
-        if lazy:
-            from sctools_amd.columnar import PackedDictionary
+        from sctools_amd.columnar import PackedDictionary
 
-            return PackedDictionary(raw, offs, bool(hn.value))
-        lst = [raw[offs[i]:offs[i + 1]].decode("utf-8") for i in range(k)]
-        if hn.value:
-            lst[0] = None
-        return lst
+        packed = PackedDictionary(*_ffi.read_dictionary(self.L.sct_gbam_dictionary, self.h, which))
+        return packed if lazy else packed.names
 
     def close(self):
         if self.h:
@@ -147,11 +99,6 @@ class _Handle:
         out = dict(zip(STAGES, list(t)))
         out["windows"] = int(self.L.sct_gbam_windows(self.h))
         return out
-
-
-def _check(rc: int):
-    if rc not in (OK, HOST):
-        raise OSError("device BAM decode failed (%d): %s" % (rc, last_error()))
 
 
 COUNT_COLUMNS = ("cell", "umi", "gene", "xf", "qhead")
@@ -168,11 +115,11 @@ def decode(path: str, metric_mode: str = "cell", device=None, timings: Optional[
     import torch
 
     from sctools_amd import _native as N
-    from sctools_amd.engine import _TORCH_DTYPES
+    from sctools_amd.engine import TORCH_DTYPES
 
     H = _Handle(path, device)
     try:
-        _check(H.rc)
+        H.check_open()
         if H.rc == HOST:
             return None
         if metric_mode == "count" and (tags is None or len(tags) != 3 or any(len(t) != 2 for t in tags)):
@@ -183,7 +130,7 @@ def decode(path: str, metric_mode: str = "cell", device=None, timings: Optional[
                 cols = {c: torch.empty(H.n, dtype=torch.int32 if c in ("cell", "umi", "gene") else torch.uint8,
                                        device=H.dev) for c in COUNT_COLUMNS}
             else:
-                cols = {c: torch.empty(H.n, dtype=_TORCH_DTYPES[c], device=H.dev) for c in N.RECORD_COLUMNS}
+                cols = {c: torch.empty(H.n, dtype=TORCH_DTYPES[c], device=H.dev) for c in N.RECORD_COLUMNS}
         except torch.cuda.OutOfMemoryError:
             return None
         ptrs = (ctypes.c_void_p * len(names_))(*[cols[c].data_ptr() for c in names_])
@@ -207,7 +154,7 @@ def inflate(path: str, device=None) -> Optional[bytes]:
     None when the device path declines the file."""
     H = _Handle(path, device)
     try:
-        _check(H.rc)
+        H.check_open()
         if H.rc == HOST:
             return None
         total = ctypes.c_uint64(0)
@@ -235,7 +182,7 @@ def decode_parts(path: str, metric_mode: str, devices, timings: Optional[dict] =
     import torch
 
     from sctools_amd import _native as N
-    from sctools_amd.engine import _TORCH_DTYPES
+    from sctools_amd.engine import TORCH_DTYPES
 
     if metric_mode not in _MODES:
         raise ValueError("decode_parts reads the cell and gene metric modes")
@@ -272,8 +219,7 @@ def decode_parts(path: str, metric_mode: str, devices, timings: Optional[dict] =
 
         each(open_one)
         for h in hs:
-            if h.rc not in (OK, HOST):
-                raise OSError("device BAM decode failed (%d): %s" % (h.rc, h.err))
+            h.check_open()
         if hs[0].rc == HOST:
             return None
         # part p starts where part p-1's walk lands: a part whose own guess disagrees (or failed
@@ -284,8 +230,7 @@ def decode_parts(path: str, metric_mode: str, devices, timings: Optional[dict] =
                 hs[p].close()
                 with torch.cuda.device(devs[p]):
                     hs[p] = _Handle(path, devs[p], p, P, first_start=land)
-                if hs[p].rc not in (OK, HOST):
-                    raise OSError("device BAM decode failed (%d): %s" % (hs[p].rc, hs[p].err))
+                hs[p].check_open()
                 if hs[p].rc == HOST:
                     return None
         cols: list = [None] * P
@@ -295,7 +240,7 @@ def decode_parts(path: str, metric_mode: str, devices, timings: Optional[dict] =
         def parse_one(p):
             h = hs[p]
             try:
-                cols[p] = {c: torch.empty(h.n, dtype=_TORCH_DTYPES[c], device=h.dev) for c in N.RECORD_COLUMNS}
+                cols[p] = {c: torch.empty(h.n, dtype=TORCH_DTYPES[c], device=h.dev) for c in N.RECORD_COLUMNS}
             except torch.cuda.OutOfMemoryError:
                 rcs[p] = HOST
                 return
@@ -306,8 +251,7 @@ def decode_parts(path: str, metric_mode: str, devices, timings: Optional[dict] =
 
         each(parse_one)
         for rc, msg in zip(rcs, msgs):
-            if rc not in (OK, HOST):
-                raise OSError("device BAM decode failed (%d): %s" % (rc, msg))
+            _check(rc, msg)
         if any(rc == HOST for rc in rcs):
             return None
         L = load()

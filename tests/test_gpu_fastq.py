@@ -279,6 +279,56 @@ def test_corrected_columns_equal_the_host_iterator():
     assert (index >= 0).any() and (index < 0).any()
 
 
+def test_a_window_smaller_than_one_record_grows(tmp_path):
+    path = str(tmp_path / "three.fastq")
+    recs = make_records(3, 9, name_lengths=(6, 8))
+    assert all(55 <= len(r) <= 75 for r in recs)  # the 16-byte window doubles until one record is whole
+    open(path, "wb").write(b"".join(recs))
+    gen = fastq.EmbeddedBarcodeGenerator(path, [CELL, MOLECULE])
+    want = host_values(gen)
+    windows = list(gen.columns(window_bytes=16))
+    assert sum(w["CR"].shape[0] for w in windows) == 3
+    for tag in ("CR", "CY", "UR", "UY"):
+        assert [bytes(row).decode() for w in windows for row in w[tag].cpu().numpy()] == want[tag], tag
+
+
+def test_text_windows_and_extract_spans_used_directly():
+    import torch
+
+    spans = [(CELL.start, CELL.end), (MOLECULE.start, MOLECULE.end)]
+    want = [w for w in fastq.EmbeddedBarcodeGenerator(R1, [CELL, MOLECULE]).columns()]
+    want = {tag: torch.cat([w[tag] for w in want]).cpu().numpy() for tag in ("CR", "CY", "UR", "UY")}
+    counts, parts = [], []
+    text = open(R1, "rb").read()
+    at = 0
+    for window in fastq.TextWindows([R1], window_bytes=2000):
+        assert window.text.is_cuda and window.n_bytes <= 2000 and len(window.host) == window.n_bytes
+        assert bytes(window.host) == text[at:at + window.n_bytes]  # a window opens where the last one's records ended
+        assert bytes(window.text[:window.n_bytes].cpu().numpy()) == bytes(window.host)
+        columns, first_flagged, flags = fastq.extract_spans(window, spans)
+        assert first_flagged == -1 and not flags[:window.n_records].any()
+        assert [tuple(t.shape) for pair in columns for t in pair] == \
+            [(window.n_records, 16)] * 2 + [(window.n_records, 10)] * 2
+        counts.append(window.n_records)
+        parts.append([t.clone() for pair in columns for t in pair])  # the next window reuses the text, not these
+        at += sum(len(ln) for ln in text[at:].splitlines(keepends=True)[:4 * window.n_records])
+    assert sum(counts) == 100 and len(counts) > 3
+    for k, tag in enumerate(("CR", "CY", "UR", "UY")):
+        assert np.array_equal(torch.cat([p[k] for p in parts]).cpu().numpy(), want[tag]), tag
+
+
+def test_fastq_metrics_with_small_windows_equals_the_default_window():
+    from sctools_amd import fastq_metrics
+
+    whole = fastq_metrics.FastqMetrics(R1, "16C10M").compute()
+    small = fastq_metrics.FastqMetrics(R1, "16C10M").compute(window_bytes=2000)
+    assert whole.n_records == small.n_records == 100 and small.n_host_rows == whole.n_host_rows
+    for field in ("barcodes", "barcode_counts", "umis", "umi_counts", "barcode_pwm", "umi_pwm", "barcode_other",
+                  "umi_other"):
+        assert np.array_equal(getattr(whole, field), getattr(small, field)), field
+    assert int(whole.barcode_counts.sum()) == 100
+
+
 # ---- the commands ----
 
 def tags_of(path):

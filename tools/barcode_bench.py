@@ -31,13 +31,10 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from sctools_amd import barcode  # noqa: E402
+from sctools_amd._ffi import ptr, stream as current_stream  # noqa: E402
 
 L = 16
 HBM_PEAK = 8.0e12
-
-
-def ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def decode(codes):
@@ -121,7 +118,7 @@ def main():
     torch.cuda.set_device(dev)
     gen = torch.Generator(device=dev)
     gen.manual_seed(7)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = current_stream(dev)
 
     wl = torch.unique(torch.randint(0, 1 << (2 * L), (args.whitelist * 2,), device=dev, generator=gen))
     wl = wl[torch.randperm(wl.numel(), device=dev, generator=gen)[:args.whitelist]].contiguous()

@@ -36,13 +36,10 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from sctools_amd import bam, bamnative, barcode, fastq, platform  # noqa: E402
+from sctools_amd._ffi import ptr, stream as current_stream  # noqa: E402
 
 HBM_PEAK = 8.0e12
 SPANS = [(0, 16), (16, 26)]
-
-
-def ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def r1_block(n, rng, whitelist=None):
@@ -95,7 +92,7 @@ def kernel_line(n_records, calls):
     c_spans = (fastq.Span * 2)(*[fastq.Span(s, e) for s, e in SPANS])
     c_seq = (ctypes.c_void_p * 2)(*[t.data_ptr() for t in seq])
     c_qual = (ctypes.c_void_p * 2)(*[t.data_ptr() for t in qual])
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = current_stream(dev)
 
     def count():
         fastq.check(lib.sct_fq_count(ptr(text), n_bytes, 1, ptr(work), work.numel(), ptr(result), stream))

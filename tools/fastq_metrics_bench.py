@@ -26,7 +26,6 @@ with the host clock (it ends in device-to-host copies), twice; the file's reads 
 8192, so the tables stay small: the figure is the reading, copying and extraction, not the table.
 """
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -39,14 +38,11 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from sctools_amd import fastq_metrics  # noqa: E402
+from sctools_amd._ffi import ptr, stream as current_stream  # noqa: E402
 
 HBM_PEAK = 8.0e12
 POOL = 1 << 20
 HOT_FRACTION = 0.05
-
-
-def ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def columns(n, dev):
@@ -71,7 +67,7 @@ def kernel_line(name, col, calls):
     pwm = torch.zeros((length, 6), dtype=torch.int64, device=dev)
     exceptions = torch.empty(n, dtype=torch.int64, device=dev)
     result = torch.zeros(4, dtype=torch.int64, device=dev)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = current_stream(dev)
 
     def init():
         fastq_metrics.check(lib.sct_fqm_table_init(ptr(table), n_slots, table.numel(), stream))
