@@ -14,7 +14,7 @@ FASTQ := sctools_amd/libsct_fastq.so
 
 SI4 := tests/native/libsct_engine_si4.so
 
-all: $(ENGINE) $(BAMDEC) $(CSVFMT) $(GBAM) $(BARCODE) $(FASTQ) oracle/liboracle.so tests/native/libfxcheck.so $(SI4)
+all: $(ENGINE) $(BAMDEC) $(CSVFMT) $(GBAM) $(BARCODE) $(FASTQ) oracle/liboracle.so tests/native/libfxcheck.so tests/native/libstdhash.so $(SI4)
 
 $(ENGINE): $(SRC) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -o $@ $(SRC) -L/opt/rocm/lib -lrccl
@@ -23,8 +23,8 @@ $(ENGINE): $(SRC) $(HDRS)
 $(SI4): $(SRC) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -DSCT_SORT_ITEMS=4 -o $@ $(SRC) -L/opt/rocm/lib -lrccl
 
-$(BAMDEC): sctools_amd/csrc/bamdec.cpp sctools_amd/csrc/bamsplit.cpp sctools_amd/csrc/bamtag.cpp sctools_amd/csrc/bamwrite.h sctools_amd/csrc/bgzf.h include/sct_bam.h
-	g++ -O3 -std=c++17 -fopenmp -fPIC -shared -Wall -o $@ sctools_amd/csrc/bamdec.cpp sctools_amd/csrc/bamsplit.cpp sctools_amd/csrc/bamtag.cpp -lz
+$(BAMDEC): sctools_amd/csrc/bamdec.cpp sctools_amd/csrc/bamsplit.cpp sctools_amd/csrc/bamtag.cpp sctools_amd/csrc/bamshards.cpp sctools_amd/csrc/bamwrite.h sctools_amd/csrc/bgzf.h include/sct_bam.h
+	g++ -O3 -std=c++17 -fopenmp -fPIC -shared -Wall -o $@ sctools_amd/csrc/bamdec.cpp sctools_amd/csrc/bamsplit.cpp sctools_amd/csrc/bamtag.cpp sctools_amd/csrc/bamshards.cpp -lz
 
 $(GBAM): sctools_amd/csrc/gbam.hip sctools_amd/csrc/inflate.h sctools_amd/csrc/bgzf.h include/sct_gbam.h include/sct_bam.h
 	$(HIPCC) $(HIPFLAGS) -o $@ sctools_amd/csrc/gbam.hip -lz
@@ -32,7 +32,7 @@ $(GBAM): sctools_amd/csrc/gbam.hip sctools_amd/csrc/inflate.h sctools_amd/csrc/b
 $(BARCODE): sctools_amd/csrc/barcode.hip sctools_amd/csrc/liberr.h include/sct_barcode.h
 	$(HIPCC) $(HIPFLAGS) -o $@ sctools_amd/csrc/barcode.hip
 
-$(FASTQ): sctools_amd/csrc/fastq.hip sctools_amd/csrc/fqmetrics.h sctools_amd/csrc/liberr.h include/sct_fastq.h include/sct_fastq_metrics.h
+$(FASTQ): sctools_amd/csrc/fastq.hip sctools_amd/csrc/fqmetrics.h sctools_amd/csrc/fqprocess.h sctools_amd/csrc/liberr.h include/sct_fastq.h include/sct_fastq_metrics.h include/sct_fastq_process.h
 	$(HIPCC) $(HIPFLAGS) -o $@ sctools_amd/csrc/fastq.hip
 
 $(CSVFMT): sctools_amd/csrc/csvfmt.cpp include/sct_csv.h
@@ -41,10 +41,14 @@ $(CSVFMT): sctools_amd/csrc/csvfmt.cpp include/sct_csv.h
 oracle/liboracle.so: oracle/sct_oracle.c include/sctools_gpu.h
 	$(MAKE) -s -C oracle liboracle.so
 
+# std::hash<std::string> itself, for tests/test_fastq_process_cpu.py
+tests/native/libstdhash.so: tests/native/stdhash.cpp
+	g++ -O2 -std=c++17 -fPIC -shared -o $@ tests/native/stdhash.cpp
+
 tests/native/libfxcheck.so: tests/native/fxcheck.cpp sctools_amd/csrc/fixedpt.h
 	g++ -O2 -std=c++17 -ffp-contract=off -fPIC -shared -o $@ tests/native/fxcheck.cpp
 
 clean:
-	rm -f $(ENGINE) $(BAMDEC) $(CSVFMT) $(GBAM) $(BARCODE) $(FASTQ) oracle/liboracle.so tests/native/libfxcheck.so $(SI4)
+	rm -f $(ENGINE) $(BAMDEC) $(CSVFMT) $(GBAM) $(BARCODE) $(FASTQ) oracle/liboracle.so tests/native/libfxcheck.so tests/native/libstdhash.so $(SI4)
 
 .PHONY: all clean

@@ -173,6 +173,29 @@ int sct_bam_attach_write(sct_bam_attach_t* h, int64_t n, int32_t n_tags, const c
  * records that no call wrote are not copied (the zip of bam.py:229 ends with its shortest input). */
 int sct_bam_attach_close(sct_bam_attach_t* h);
 
+/* The shard writer of FastqProcess (bamshards.cpp): `n` BGZF files that grow together.
+ *
+ * sct_bam_shards_open creates paths[0..n).  headers[i] (`headers` itself may be NULL) is file i's
+ * SAM header text, written as a BAM header with no references in members of its own; a file
+ * without one gets no header at all and holds the appended bytes alone (a .fastq.gz shard: a BGZF
+ * file is a multi-member gzip).  If a file cannot be created, those created before it are removed. */
+typedef struct sct_bam_shards sct_bam_shards_t;
+int sct_bam_shards_open(const char* const* paths, const char* const* headers, int32_t n, int32_t level,
+                        int32_t n_threads, sct_bam_shards_t** out);
+
+/* Appends data[bounds[i] .. bounds[i + 1]) to file i, for every i (bounds has n + 1 entries and
+ * does not decrease).  Full 0xff00-byte members are deflated in parallel and written; the rest
+ * waits for the next call, so the members do not depend on how the caller cut the stream.  On an
+ * I/O error every file is removed and only close or abort may follow. */
+int sct_bam_shards_append(sct_bam_shards_t* h, const uint8_t* data, const int64_t* bounds);
+
+/* Writes every file's last member and EOF member, closes the files and frees the handle.  On an
+ * error every file is removed. */
+int sct_bam_shards_close(sct_bam_shards_t* h);
+
+/* Closes and removes every file and frees the handle. */
+void sct_bam_shards_abort(sct_bam_shards_t* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 """python -m sctools_amd <Command> [args]  (CalculateCellMetrics, CalculateGeneMetrics,
 MergeCellMetrics, MergeGeneMetrics, SplitBam, TagSortBam, VerifyBamSort, CreateCountMatrix,
-MergeCountMatrices, CorrectBarcodes, Attach10xBarcodes, AttachBarcodes, FastqMetrics)."""
+MergeCountMatrices, CorrectBarcodes, Attach10xBarcodes, AttachBarcodes, FastqMetrics, FastqProcess,
+FastqSlideseq)."""
 import sys
 
 from sctools_amd.platform import COMMANDS

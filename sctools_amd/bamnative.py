@@ -51,6 +51,10 @@ PROTOTYPES = {
     "sct_bam_attach_n": (_i64, [_vp]),
     "sct_bam_attach_write": (_int, [_vp, _i64, _i32, _str, _P(_vp), _P(_i64), _P(_vp), _P(_i64)]),
     "sct_bam_attach_close": (_int, [_vp]),
+    "sct_bam_shards_open": (_int, [_P(_str), _P(_str), _i32, _i32, _i32, _P(_vp)]),
+    "sct_bam_shards_append": (_int, [_vp, _vp, _P(_i64)]),
+    "sct_bam_shards_close": (_int, [_vp]),
+    "sct_bam_shards_abort": (None, [_vp]),
 }
 EXPORTED = tuple(PROTOTYPES)
 
@@ -266,3 +270,54 @@ class TagAttacher:
             self._lib.sct_bam_attach_close(h)
         if os.path.exists(self.out_path):
             os.remove(self.out_path)
+
+
+class ShardWriter:
+    """sct_bam_shards_*: ``paths`` created together and appended to together.  ``headers`` is None or one
+    SAM header text (or None) per path: a file with one is a BAM with no references, a file without
+    one holds the appended bytes alone (a ``.fastq.gz`` shard).  A context manager; leaving it on an
+    exception removes every file."""
+
+    def __init__(self, paths, headers=None, level: int = 6, threads: int = 0):
+        self._lib = load()
+        self._h = ctypes.c_void_p()
+        self.paths = [os.fspath(p) for p in paths]
+        n = len(self.paths)
+        if headers is not None and len(headers) != n:
+            raise ValueError("%d headers for %d paths" % (len(headers), n))
+        c_paths = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(p) for p in self.paths])
+        c_headers = None
+        if headers is not None:
+            c_headers = (ctypes.c_char_p * max(n, 1))(*[None if h is None else h.encode("utf-8") for h in headers])
+        check(self._lib.sct_bam_shards_open(c_paths, c_headers, n, int(level), int(threads), ctypes.byref(self._h)))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        else:
+            self.abort()
+
+    def append(self, data, bounds) -> None:
+        """``data`` is a contiguous uint8 numpy array; file i gets ``data[bounds[i]:bounds[i + 1]]``."""
+        b = np.ascontiguousarray(bounds, dtype=np.int64)
+        if b.shape != (len(self.paths) + 1,):
+            raise ValueError("bounds must have %d entries, got %s" % (len(self.paths) + 1, b.shape))
+        d = np.ascontiguousarray(data, dtype=np.uint8)
+        if b[-1] > d.size:
+            raise ValueError("the bounds end at %d, the data has %d bytes" % (int(b[-1]), d.size))
+        check(self._lib.sct_bam_shards_append(self._h, d.ctypes.data if d.size else None,
+                                              b.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+
+    def close(self) -> None:
+        if self._h:
+            h, self._h = self._h, ctypes.c_void_p()
+            check(self._lib.sct_bam_shards_close(h))
+
+    def abort(self) -> None:
+        """Close and remove every file."""
+        if self._h:
+            h, self._h = self._h, ctypes.c_void_p()
+            self._lib.sct_bam_shards_abort(h)

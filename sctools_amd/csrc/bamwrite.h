@@ -61,17 +61,25 @@ inline int write_bam_file(const char* out_path, const std::string& header, const
 class BamStreamWriter {
  public:
   ~BamStreamWriter() {
-    for (auto& z : zs_) deflateEnd(&z);
+    for (auto& z : own_) deflateEnd(&z);
     if (f_) fclose(f_);
   }
-  int open(const char* out_path, const std::string& header, int level, int n_threads) {
+  // `shared`, when given, is a pool of at least n_threads raw-deflate states at `level` that outlives
+  // the writer and that no other writer uses at the same time (sct_bam_shards_*: one pool per handle)
+  int open(const char* out_path, const std::string& header, int level, int n_threads,
+           std::vector<z_stream>* shared = nullptr) {
     path_ = out_path;
     level_ = level;
     n_threads_ = n_threads;
-    zs_.resize(n_threads);
-    for (auto& z : zs_) {
-      memset(&z, 0, sizeof(z));
-      deflateInit2(&z, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY);
+    if (shared) {
+      zs_ = shared;
+    } else {
+      own_.resize(n_threads);
+      for (auto& z : own_) {
+        memset(&z, 0, sizeof(z));
+        deflateInit2(&z, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY);
+      }
+      zs_ = &own_;
     }
     f_ = fopen(out_path, "wb");
     if (!f_) return fail(SCT_BAM_EIO, "cannot create %s", out_path);
@@ -111,7 +119,7 @@ class BamStreamWriter {
 #pragma omp parallel for num_threads(n_threads_) schedule(dynamic, 1) reduction(| : bad)
     for (long k = 0; k < (long)np; k++) {
       const size_t o = (size_t)k * kBgzfMaxInput;
-      if (!bgzf_block(src + o, std::min(kBgzfMaxInput, total - o), level_, zs_[omp_get_thread_num()], z[k])) bad = 1;
+      if (!bgzf_block(src + o, std::min(kBgzfMaxInput, total - o), level_, (*zs_)[omp_get_thread_num()], z[k])) bad = 1;
     }
     if (bad) return fail(SCT_BAM_EIO, "deflate failed");
     for (size_t k = 0; k < np; k++)
@@ -120,7 +128,8 @@ class BamStreamWriter {
   }
   std::string path_;
   int level_ = 6, n_threads_ = 1;
-  std::vector<z_stream> zs_;
+  std::vector<z_stream> own_;
+  std::vector<z_stream>* zs_ = nullptr;
   std::vector<uint8_t> pending_;
   FILE* f_ = nullptr;
 };
