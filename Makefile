@@ -14,7 +14,7 @@ FASTQ := sctools_amd/libsct_fastq.so
 
 SI4 := tests/native/libsct_engine_si4.so
 
-all: $(ENGINE) $(BAMDEC) $(CSVFMT) $(GBAM) $(BARCODE) $(FASTQ) oracle/liboracle.so tests/native/libfxcheck.so tests/native/libstdhash.so $(SI4)
+all: $(ENGINE) $(BAMDEC) $(CSVFMT) $(GBAM) $(BARCODE) $(FASTQ) oracle/liboracle.so tests/native/libfxcheck.so tests/native/libstdhash.so tests/native/libtsround.so $(SI4)
 
 $(ENGINE): $(SRC) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -o $@ $(SRC) -L/opt/rocm/lib -lrccl
@@ -45,10 +45,14 @@ oracle/liboracle.so: oracle/sct_oracle.c include/sctools_gpu.h
 tests/native/libstdhash.so: tests/native/stdhash.cpp
 	g++ -O2 -std=c++17 -fPIC -shared -o $@ tests/native/stdhash.cpp
 
+# the six-digit text round trip of tsmetrics.h on the host, beside glibc's (tests/test_tagsort_native_cpu.py)
+tests/native/libtsround.so: tests/native/tsround.cpp sctools_amd/csrc/tsround.h
+	g++ -O2 -std=c++17 -ffp-contract=off -fPIC -shared -o $@ tests/native/tsround.cpp
+
 tests/native/libfxcheck.so: tests/native/fxcheck.cpp sctools_amd/csrc/fixedpt.h
 	g++ -O2 -std=c++17 -ffp-contract=off -fPIC -shared -o $@ tests/native/fxcheck.cpp
 
 clean:
-	rm -f $(ENGINE) $(BAMDEC) $(CSVFMT) $(GBAM) $(BARCODE) $(FASTQ) oracle/liboracle.so tests/native/libfxcheck.so tests/native/libstdhash.so $(SI4)
+	rm -f $(ENGINE) $(BAMDEC) $(CSVFMT) $(GBAM) $(BARCODE) $(FASTQ) oracle/liboracle.so tests/native/libfxcheck.so tests/native/libstdhash.so tests/native/libtsround.so $(SI4)
 
 .PHONY: all clean

@@ -45,6 +45,13 @@ extern "C" {
                                 * and the query name, ranked into a fourth dictionary (column "qname",
                                 * int32); nothing is validated, an empty file is 0 records */
 
+#define SCT_BAM_TAGSORT 4     /* the native TagSort's per-read rule (fastqpreprocessing/src/htslib_tagsort.cpp:
+                                * 106-218) on the three named string tags (barcode, umi, gene): nothing is
+                                * validated; a missing tag and the value "-" are the missing id; the unmapped
+                                * bit is refID == -1; the gq_* columns cover all base qualities; CY / UY
+                                * lengths of 0 are kept; the perfect-barcode bits are strcmp(tag or "None",
+                                * CR / UR or ""); an empty file is 0 records */
+
 #define SCT_BAM_TAG_CB 0
 #define SCT_BAM_TAG_UB 1
 #define SCT_BAM_TAG_GE 2

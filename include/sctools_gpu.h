@@ -269,6 +269,68 @@ int sct_verify_sort(const sct_plan_t* plan, const sct_records_t* rec, const int3
                     int32_t order, void* workspace, size_t workspace_bytes,
                     int64_t* first_violation /* host */, void* stream);
 
+/* ---- native TagSort metrics (fastqpreprocessing/src: tagsort.cpp:185-273,
+ *      metricgatherer.{h,cpp}) ----
+ * The gatherer of the reference's TagSort binary on records already sorted by the tag triplet.
+ * The three id columns are positional here: `cell` holds the FIRST tag's ids, `umi` the SECOND's,
+ * `gene` the THIRD's, whichever tags those are, each id the rank of the tag string in byte order
+ * (a missing tag is the string "None"); sct_tag_sort with SCT_ORDER_CELL_UMI_GENE then gives the
+ * reference's order, equal triplets in input order.  The other columns carry the native per-read
+ * rule (htslib_tagsort.cpp:106-218): SCT_B_UNMAPPED is refID == -1, the gq_* columns cover all
+ * base qualities of the record, lengths may be 0.
+ *
+ * plan: n_records; mode SCT_MODE_CELL or SCT_MODE_GENE (the metric type); n_cell_ids / n_umi_ids /
+ * n_gene_ids = the first / second / third dictionary sizes; max_entities = `capacity`, the rows
+ * the outputs hold (0 = n_records + 1, the most there can be).  float_mode and flags are ignored.
+ *
+ * Rows follow MetricGatherer::ingestLine (metricgatherer.cpp:152-200): a record whose first id has
+ * first_drop set is skipped; a row closes before a record whose first tag differs from that of the
+ * last mapped record counted so far; one more row always follows the last record.
+ * out_ints [capacity][SCT_TS_NI] int64, out_sums [capacity][SCT_TS_NF] double: per float stream
+ * (SCT_TS_S_*) count, sum and sum of squares, added in record order in double, of
+ * strtof(sprintf("%g", float32 ratio)): the value the gatherer reads back from its text file.
+ * Means, variances and ratios are left to the caller (metricgatherer.h:28-41, .cpp:101-150). */
+#define SCT_TS_NI 21
+#define SCT_TS_I_N_READS 0
+#define SCT_TS_I_PERFECT_MOLECULE_BARCODES 1
+#define SCT_TS_I_READS_MAPPED_EXONIC 2
+#define SCT_TS_I_READS_MAPPED_INTRONIC 3
+#define SCT_TS_I_READS_MAPPED_UTR 4
+#define SCT_TS_I_READS_MAPPED_UNIQUELY 5
+#define SCT_TS_I_READS_MAPPED_MULTIPLE 6
+#define SCT_TS_I_DUPLICATE_READS 7
+#define SCT_TS_I_SPLICED_READS 8
+#define SCT_TS_I_N_MOLECULES 9
+#define SCT_TS_I_N_FRAGMENTS 10
+#define SCT_TS_I_FRAGMENTS_SINGLE 11
+#define SCT_TS_I_MOLECULES_SINGLE 12
+#define SCT_TS_I_PERFECT_CELL_BARCODES 13    /* cell */
+#define SCT_TS_I_READS_MAPPED_INTERGENIC 14  /* cell */
+#define SCT_TS_I_READS_UNMAPPED 15           /* cell: XF absent or empty, over all reads */
+#define SCT_TS_I_N_MITO_MOLECULES 16         /* cell: reads whose third tag is mitochondrial */
+#define SCT_TS_I_N_K1 17        /* cell: distinct third tags (n_genes); gene: distinct second tags */
+#define SCT_TS_I_K1_MULTIPLE 18 /* ... of those, seen more than once */
+#define SCT_TS_I_N_MITO_GENES 19 /* cell */
+#define SCT_TS_I_NAME 20        /* first-tag id the row is named after; -1: the empty name */
+
+#define SCT_TS_NF 12 /* [stream][count, sum, sum2] */
+#define SCT_TS_S_UY 0  /* molecule_barcode_fraction_bases_above_30 */
+#define SCT_TS_S_GQF 1 /* genomic_reads_fraction_bases_quality_above_30 */
+#define SCT_TS_S_GQ 2  /* genomic_read_quality */
+#define SCT_TS_S_CY 3  /* cell_barcode_fraction_bases_above_30 (cell) */
+
+/* Device workspace bytes for sct_tagsort_metrics with this plan. */
+int sct_tagsort_metrics_workspace_size(const sct_plan_t* plan, size_t* bytes);
+
+/* first_drop: device uint8 per first id ("None"; for gene, a name with a comma).  third_is_mito:
+ * device uint8 per third id (cell; may be NULL for gene).  *n_rows (host) = the rows written.
+ * If they exceed the capacity the call returns SCT_ENOMEM with *n_rows set and the outputs
+ * unwritten.  Records not sorted by the triplet, or an id outside its dictionary, give SCT_EINVAL.
+ * Synchronizes `stream`. */
+int sct_tagsort_metrics(const sct_plan_t* plan, const sct_records_t* rec, const uint8_t* first_drop,
+                        const uint8_t* third_is_mito, void* workspace, size_t workspace_bytes,
+                        int64_t* out_ints, double* out_sums, int64_t* n_rows /* host */, void* stream);
+
 /* ---- multi-GPU for unsorted input: cell bins exchanged between devices ----
  * The reference's route for an unsorted BAM: SplitBam gives every cell barcode a bin
  * (bam.py:439-448), writes each input's records to their bins (write_barcodes_to_bins,

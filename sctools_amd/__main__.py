@@ -1,7 +1,7 @@
 """python -m sctools_amd <Command> [args]  (CalculateCellMetrics, CalculateGeneMetrics,
 MergeCellMetrics, MergeGeneMetrics, SplitBam, TagSortBam, VerifyBamSort, CreateCountMatrix,
 MergeCountMatrices, CorrectBarcodes, Attach10xBarcodes, AttachBarcodes, FastqMetrics, FastqProcess,
-FastqSlideseq)."""
+FastqSlideseq, TagSort)."""
 import sys
 
 from sctools_amd.platform import COMMANDS

@@ -13,6 +13,7 @@ from sctools_amd import _ffi
 SCT_ABI_VERSION = 2
 SCT_NI, SCT_NF, SCT_NP = 24, 12, 64
 SCT_P_FLOAT_BASE, SCT_P_STREAM_LANES = 24, 8
+SCT_ENOMEM = -3
 
 MODE_CELL, MODE_GENE, MODE_GENE_GROUPED = 0, 1, 2
 FLOAT_EXACT_SUM, FLOAT_WELFORD = 0, 1
@@ -26,6 +27,13 @@ I_N_K1, I_K1_MULTI, I_MITO_GENES, I_MITO_READS, I_ENTITY = 19, 20, 21, 22, 23
 # output float columns
 F_UY_MEAN, F_UY_VAR, F_GQF_MEAN, F_GQF_VAR, F_GQ_MEAN, F_GQ_VAR = 0, 1, 2, 3, 4, 5
 F_RPM, F_RPF, F_FPM, F_CY_VAR, F_CY_MEAN, F_PCT_MITO = 6, 7, 8, 9, 10, 11
+
+# native TagSort rows (sct_tagsort_metrics): int columns, then [stream][count, sum, sum2]
+SCT_TS_NI, SCT_TS_NF = 21, 12
+(TS_N_READS, TS_PERFECT_UMI, TS_EXONIC, TS_INTRONIC, TS_UTR, TS_UNIQUE, TS_MULTIPLE, TS_DUP, TS_SPLICED, TS_N_MOL,
+ TS_N_FRAG, TS_FRAG_SINGLE, TS_MOL_SINGLE, TS_PERFECT_CB, TS_INTERGENIC, TS_UNMAPPED, TS_MITO_READS, TS_N_K1,
+ TS_K1_MULTI, TS_MITO_GENES, TS_NAME) = range(21)
+TS_S_UY, TS_S_GQF, TS_S_GQ, TS_S_CY = 0, 1, 2, 3
 
 RECORD_COLUMNS = ("cell", "umi", "gene", "ref", "pos", "gq_sum", "gq_len", "gq_gt30", "bits", "xf",
                   "cy_gt30", "cy_len", "uy_gt30", "uy_len")
@@ -122,6 +130,8 @@ PROTOTYPES = {
     "sct_bin_records": (_int, [_plan, _rec, _vp, _vp, _i32, _rec, _vp, _vp, _vp, _sz, _vp]),
     "sct_exchange_counts": (_int, [_vp, _vp, _i32, _vp, _vp]),
     "sct_exchange_records": (_int, [_rec, _vp, _P(_i64), _P(_i64), _i32, _rec, _vp, _vp, _vp]),
+    "sct_tagsort_metrics_workspace_size": (_int, [_plan, _P(_sz)]),
+    "sct_tagsort_metrics": (_int, [_plan, _rec, _vp, _vp, _vp, _sz, _vp, _vp, _P(_i64), _vp]),
 }
 EXPORTED = tuple(PROTOTYPES)
 

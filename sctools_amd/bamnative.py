@@ -25,8 +25,9 @@ class TypedTagValue(Exception):
     """A dictionary tag holds a float or array value (or, for the sort keys, an integer): the native
     decoder cannot key it as the Python reader does, so the caller decodes with the Python reader
     (include/sct_bam.h SCT_BAM_ETYPED)."""
-CELL_METRICS, GENE_METRICS, COUNT_MATRIX, SORT_KEYS = 0, 1, 2, 3
-_MODES = {"cell": CELL_METRICS, "gene": GENE_METRICS, "count": COUNT_MATRIX, "sortkeys": SORT_KEYS}
+CELL_METRICS, GENE_METRICS, COUNT_MATRIX, SORT_KEYS, TAGSORT = 0, 1, 2, 3, 4
+_MODES = {"cell": CELL_METRICS, "gene": GENE_METRICS, "count": COUNT_MATRIX, "sortkeys": SORT_KEYS,
+          "tagsort": TAGSORT}
 
 _P = ctypes.POINTER
 _vp, _i32, _i64, _int, _str = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int, ctypes.c_char_p
@@ -79,7 +80,11 @@ def decode(path: str, metric_mode: str = "cell", threads: int = 0, tags=("CB", "
     metric_mode "sortkeys" (TagSortBam / VerifyBamSort): cell / umi / gene are the ranks of the
     three ``tags`` (a missing tag and an empty value both rank first, as "" does),
     ``arrays["qname"]`` the rank of the query name, and a fourth name list holds the query
-    names in rank order."""
+    names in rank order.
+
+    metric_mode "tagsort" (the native TagSort's per-read rule, :mod:`sctools_amd.tagsort`): ``tags``
+    are the barcode, umi and gene tag; a missing tag and the value ``-`` are the None id; nothing
+    is validated."""
     from sctools_amd.columnar import COLUMNS, PackedDictionary
 
     L = load()

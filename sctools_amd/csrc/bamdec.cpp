@@ -361,6 +361,127 @@ int parse_count_record(const uint8_t* d, uint32_t bs, const char* tags, bool sor
   return typed_keys(o, sortkeys, e);
 }
 
+// TagSort mode: the per-read stage of the reference's native TagSort (fastqpreprocessing/src/
+// htslib_tagsort.cpp:106-218).  The three dictionary tags are named by `tags` (barcode, umi, gene);
+// every string tag read here goes through get_Ztag_or_default, so the value "-" counts as missing.
+// Nothing is validated: lengths of 0 are kept (the ratios are NaN there), `mapped` is refID != -1
+// whatever the flag says, and the quality columns cover ALL base qualities of the record.
+int parse_tagsort_record(const uint8_t* d, uint32_t bs, const char* tags, Parsed& o, RecErr& e) {
+  if (bs < 32) {
+    e.code = SCT_BAM_EFORMAT;
+    e.msg = "truncated BAM record";
+    return -1;
+  }
+  const int32_t ref = (int32_t)rd32(d), pos = (int32_t)rd32(d + 4);
+  const uint32_t l_read_name = d[8];
+  const uint32_t n_cigar = rd16(d + 12), flag = rd16(d + 14);
+  const uint32_t l_seq = rd32(d + 16);
+  const uint64_t cig_off = 32 + (uint64_t)l_read_name;
+  const uint64_t qual_off = cig_off + 4ull * n_cigar + ((uint64_t)l_seq + 1) / 2;
+  const uint64_t tag_off = qual_off + l_seq;
+  if (tag_off > bs) {
+    e.code = SCT_BAM_EFORMAT;
+    e.msg = "truncated BAM record";
+    return -1;
+  }
+  const uint8_t* cig = d + cig_off;
+  const uint8_t* qual = d + qual_off;
+  TagVal cr, cy, ur, uy, xf, nh;
+  o.cb = TagVal(), o.ub = TagVal(), o.ge = TagVal();
+  bool seen[9] = {false, false, false, false, false, false, false, false, false};
+  const uint8_t* p = d + tag_off;
+  const uint8_t* end = d + bs;
+  while (p + 3 <= end) {
+    const char a = (char)p[0], b = (char)p[1], t = (char)p[2];
+    p += 3;
+    TagVal v;
+    const size_t used = read_tag(p, end, t, &v);
+    if (!used || p + used > end) {
+      e.code = SCT_BAM_EFORMAT;
+      e.msg = std::string("unsupported or truncated BAM tag type ") + t;
+      return -1;
+    }
+    // bam_aux_get returns the first occurrence of a tag
+    const auto first = [&](int k, TagVal& dst) {
+      if (!seen[k]) seen[k] = true, dst = v;
+    };
+    if (a == tags[0] && b == tags[1]) first(0, o.cb);
+    if (a == tags[2] && b == tags[3]) first(1, o.ub);
+    if (a == tags[4] && b == tags[5]) first(2, o.ge);
+    if (a == 'C' && b == 'R') first(3, cr);
+    if (a == 'C' && b == 'Y') first(4, cy);
+    if (a == 'U' && b == 'R') first(5, ur);
+    if (a == 'U' && b == 'Y') first(6, uy);
+    if (a == 'X' && b == 'F') first(7, xf);
+    if (a == 'N' && b == 'H') first(8, nh);
+    p += used;
+  }
+  const auto is_z = [](const TagVal& v) { return v.is_str && (v.type == 'Z' || v.type == 'H'); };
+  for (const TagVal* v : {&o.cb, &o.ub, &o.ge})  // the three tags are string tags (bam_aux2Z)
+    if (v->present && !is_z(*v)) {
+      e.code = SCT_BAM_ETYPED;
+      e.msg = std::string("a dictionary tag holds a value of type ") + v->type;
+      return -1;
+    }
+  // get_Ztag_or_default: a missing tag, a non-string one here, and the value "-" give the default
+  for (TagVal* v : {&o.cb, &o.ub, &o.ge, &cr, &cy, &ur, &uy, &xf})
+    if (v->present && (!is_z(*v) || (v->n == 1 && v->s[0] == '-'))) *v = TagVal();
+  // strcmp(tag or "None", raw or ""): C strings, so a value ends at its first NUL
+  const auto perfect = [](const TagVal& tag, const TagVal& raw) {
+    const char* a = tag.present ? tag.s : "None";
+    const size_t an = tag.present ? strnlen(tag.s, tag.n) : 4;
+    const size_t bn = raw.present ? strnlen(raw.s, raw.n) : 0;
+    return an == bn && (bn == 0 || memcmp(a, raw.s, bn) == 0);
+  };
+  uint8_t bits = 0;
+  if (o.cb.present) bits |= B_HAS_CB;
+  if (perfect(o.cb, cr)) bits |= B_PERFECT_CB;
+  if (perfect(o.ub, ur)) bits |= B_PERFECT_UMI;
+  uint32_t cg = 0, cl = 0, ug = 0, ul = 0;
+  if (cy.present) {
+    cl = (uint32_t)strnlen(cy.s, cy.n);
+    for (uint32_t k = 0; k < cl; k++) cg += (uint8_t)((uint8_t)cy.s[k] - 33) > 30 ? 1u : 0u;  // uint8_t qual_score
+  }
+  if (uy.present) {
+    ul = (uint32_t)strnlen(uy.s, uy.n);
+    for (uint32_t k = 0; k < ul; k++) ug += ((int)(uint8_t)uy.s[k] - 33) > 30 ? 1u : 0u;  // int arithmetic
+  }
+  uint8_t x = XF_ABSENT;
+  if (xf.present && strnlen(xf.s, xf.n) > 0) {
+    const std::string s(xf.s, strnlen(xf.s, xf.n));
+    x = XF_OTHER;
+    if (s == "CODING") x = XF_CODING;
+    else if (s == "INTRONIC") x = XF_INTRONIC;
+    else if (s == "UTR") x = XF_UTR;
+    else if (s == "INTERGENIC") x = XF_INTERGENIC;
+  }
+  if (ref == -1) bits |= B_UNMAPPED;
+  if (nh.present && !nh.is_str && !nh.raw && nh.i == 1) bits |= B_NH1;
+  for (uint32_t k = 0; k < n_cigar; k++) {
+    const uint32_t c = rd32(cig + 4 * k);
+    if ((c & 0xF) == 3 && (c >> 4) != 0) {
+      bits |= B_SPLICED;
+      break;
+    }
+  }
+  if (flag & 0x10) bits |= B_REVERSE;
+  if (flag & 0x400) bits |= B_DUPLICATE;
+  uint64_t sum = 0;
+  uint32_t g = 0;
+  for (uint32_t k = 0; k < l_seq; k++) {
+    sum += qual[k];
+    g += qual[k] > 30 ? 1u : 0u;
+  }
+  if (l_seq > 0xFFFF || sum > 0xFFFF || cl > 0xFF || ul > 0xFF) {
+    e.code = SCT_BAM_VALUEERROR;
+    e.msg = "record exceeds the 32-byte columnar limits";
+    return -1;
+  }
+  o.ref = ref, o.pos = pos, o.gq_sum = (uint32_t)sum, o.gq_len = l_seq, o.gq_gt30 = g;
+  o.cy_gt30 = cg, o.cy_len = cl, o.uy_gt30 = ug, o.uy_len = ul, o.bits = bits, o.xf = x;
+  return 0;
+}
+
 // Per-thread direct-mapped cache in front of the shared tables: cell-sorted input repeats
 // the CB of the previous record and hot genes repeat constantly, so most lookups never take
 // a stripe lock.
@@ -431,12 +552,13 @@ int sct_bam_decode_tags(const char* path, int32_t metric_mode, const char* tags,
   if (out) *out = nullptr;
   if (bad_record) *bad_record = -1;
   if (!path || !out || !tags) return fail(SCT_BAM_EIO, "NULL argument");
-  if (metric_mode < SCT_BAM_CELL_METRICS || metric_mode > SCT_BAM_SORT_KEYS)
+  if (metric_mode < SCT_BAM_CELL_METRICS || metric_mode > SCT_BAM_TAGSORT)
     return fail(SCT_BAM_EIO, "unknown decode mode %d", metric_mode);
   if (strlen(tags) != 6) return fail(SCT_BAM_EIO, "tags must name three two-character tags");
   const bool sortkeys = metric_mode == SCT_BAM_SORT_KEYS;
   const bool counting = metric_mode == SCT_BAM_COUNT_MATRIX;
-  const bool generic = counting || sortkeys;  // named tags, no validation
+  const bool tagsort = metric_mode == SCT_BAM_TAGSORT;
+  const bool generic = counting || sortkeys || tagsort;  // named tags, no validation
   if (!generic && memcmp(tags, "CBUBGE", 6) != 0) return fail(SCT_BAM_EIO, "the metric modes read CB / UB / GE");
   const bool is_cell = metric_mode == SCT_BAM_CELL_METRICS;
   if (n_threads <= 0) n_threads = omp_get_max_threads();
@@ -575,7 +697,9 @@ int sct_bam_decode_tags(const char* path, int32_t metric_mode, const char* tags,
         const uint32_t bs = rd32(buf.data() + starts[i]);
         const char* qn = nullptr;
         uint32_t qlen = 0;
-        if (generic ? parse_count_record(d, bs, tags, sortkeys, o, &qn, &qlen, e) : parse_record(d, bs, is_cell, o, e)) {
+        if (tagsort   ? parse_tagsort_record(d, bs, tags, o, e)
+            : generic ? parse_count_record(d, bs, tags, sortkeys, o, &qn, &qlen, e)
+                      : parse_record(d, bs, is_cell, o, e)) {
           std::lock_guard<std::mutex> lk(err_m);
           if (base + i < first_bad.load()) {
             first_bad = base + i;

@@ -40,6 +40,7 @@
 #include "reduce.h"
 #include "segment.h"
 #include "tagsort.h"
+#include "tsmetrics.h"
 #include "util.h"
 
 using namespace sct;
@@ -1582,6 +1583,114 @@ int sct_finalize_partials(int32_t mode, const int64_t* partials, int64_t rows, i
   hipStream_t s = (hipStream_t)stream;
   LAUNCH("finalize", k_finalize, dim3((unsigned)cdiv(rows * kFinThreads, kBlock)), dim3(kBlock), s, partials, rows, (int)mode, 1,
          (const int64_t*)nullptr, out_ints, out_floats);
+  return SCT_OK;
+}
+
+// ---- native TagSort metrics (tsmetrics.h) ----
+static int ts_check_plan(const sct_plan_t* plan, int64_t* capacity) {
+  if (!plan) return fail(SCT_EINVAL, "NULL plan");
+  // the hash tables have the power of two >= 2 n slots, indexed with 32 bits
+  if (plan->n_records < 0 || plan->n_records > (int64_t)1 << 30)
+    return fail(SCT_EINVAL, "n_records %lld out of range [0, 2^30]", (long long)plan->n_records);
+  if (plan->mode != SCT_MODE_CELL && plan->mode != SCT_MODE_GENE)
+    return fail(SCT_EINVAL, "TagSort metrics: mode must be SCT_MODE_CELL or SCT_MODE_GENE, not %d", plan->mode);
+  if (plan->n_cell_ids <= 0 || plan->n_gene_ids <= 0 || plan->n_umi_ids <= 0)
+    return fail(SCT_EINVAL, "dictionary sizes must be positive");
+  if (plan->max_entities < 0 || plan->max_entities > plan->n_records + 1)
+    return fail(SCT_EINVAL, "capacity (max_entities) %lld outside [0, n_records + 1]", (long long)plan->max_entities);
+  *capacity = plan->max_entities ? plan->max_entities : plan->n_records + 1;
+  return SCT_OK;
+}
+
+int sct_tagsort_metrics_workspace_size(const sct_plan_t* plan, size_t* bytes) {
+  int64_t capacity = 0;
+  int rc = ts_check_plan(plan, &capacity);
+  if (rc) return rc;
+  if (!bytes) return fail(SCT_EINVAL, "bytes is NULL");
+  *bytes = ts_layout(plan->n_records, plan->n_cell_ids, capacity).total;
+  return SCT_OK;
+}
+
+int sct_tagsort_metrics(const sct_plan_t* plan, const sct_records_t* rec, const uint8_t* first_drop,
+                        const uint8_t* third_is_mito, void* workspace, size_t workspace_bytes, int64_t* out_ints,
+                        double* out_sums, int64_t* n_rows, void* stream) {
+  last_error().clear();
+  int64_t capacity = 0;
+  int rc = ts_check_plan(plan, &capacity);
+  if (rc) return rc;
+  if (!rec || rec->n != plan->n_records) return fail(SCT_EINVAL, "records.n != plan.n_records");
+  if (!first_drop || !out_ints || !out_sums || !n_rows) return fail(SCT_EINVAL, "NULL argument");
+  const bool cell = plan->mode == SCT_MODE_CELL;
+  if (cell && !third_is_mito) return fail(SCT_EINVAL, "third_is_mito is NULL");
+  const int64_t n = rec->n;
+  const TsLayout L = ts_layout(n, plan->n_cell_ids, capacity);
+  if (!workspace || workspace_bytes < L.total)
+    return fail(SCT_ENOMEM, "workspace too small (%zu < %zu)", workspace_bytes, L.total);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t ne = (size_t)plan->n_cell_ids;
+  TsEnt ent{at<int32_t>(workspace, L.start), at<int32_t>(workspace, L.end), at<int32_t>(workspace, L.fm),
+            at<int32_t>(workspace, L.prev), at<int32_t>(workspace, L.rowbase)};
+  TsCtl* ctl = at<TsCtl>(workspace, L.ctl);
+  int32_t* row_start = at<int32_t>(workspace, L.row_start);
+  uint4* xv = at<uint4>(workspace, L.xv);
+  TsTable ft{at<uint32_t>(workspace, L.f_owner), at<uint32_t>(workspace, L.f_cnt), L.slots - 1};
+  TsTable kt{at<uint32_t>(workspace, L.k_owner), at<uint32_t>(workspace, L.k_cnt), L.slots - 1};
+  FillBatch fb;
+  fb.add(ent.start, 4 * ne, 0xFF);
+  fb.add(ent.end, 4 * ne, 0);
+  fb.add(ent.fm, 4 * ne, 0x7F);
+  fb.add(ctl, sizeof(TsCtl), 0xFF);
+  fb.add(ft.owner, 4 * (size_t)L.slots, 0xFF);
+  fb.add(ft.cnt, 4 * (size_t)L.slots, 0);
+  fb.add(kt.owner, 4 * (size_t)L.slots, 0xFF);
+  fb.add(kt.cnt, 4 * (size_t)L.slots, 0);
+  rc = launch_fills(fb, s);
+  if (rc) return rc;
+  const unsigned rec_blocks = (unsigned)cdiv(n, kBlock);
+  if (n > 0) {
+    LAUNCH_N("ts_mark", n, k_ts_mark, dim3(rec_blocks), dim3(kBlock), s, *rec, n, (uint32_t)plan->n_cell_ids,
+             (uint32_t)plan->n_umi_ids, (uint32_t)plan->n_gene_ids, first_drop, ent, ctl);
+  }
+  LAUNCH_N("ts_ent_scan", plan->n_cell_ids, k_ts_ent_scan, dim3(1), dim3(kTsScanBlock), s, ent, plan->n_cell_ids, ctl);
+  TsCtl h;
+  rc = readback(&h, ctl, sizeof(h), s);
+  if (rc) return rc;
+  if (h.bad_id != ~0ull) return fail(SCT_EINVAL, "record %llu has a tag id outside its dictionary", h.bad_id);
+  if (h.unsorted != ~0ull)
+    return fail(SCT_EINVAL, "records are not sorted by (first, second, third): record %llu is before its predecessor",
+                h.unsorted);
+  const int64_t rows = h.boundaries + 1;
+  *n_rows = rows;
+  if (rows > capacity)
+    return fail(SCT_ENOMEM, "%lld rows exceed the capacity of %lld", (long long)rows, (long long)capacity);
+  fb.add(out_ints, sizeof(int64_t) * SCT_TS_NI * (size_t)rows, 0);
+  fb.add(out_sums, sizeof(double) * SCT_TS_NF * (size_t)rows, 0);
+  rc = launch_fills(fb, s);
+  if (rc) return rc;
+  // the final row's name; the closed rows' names come from the records that close them
+  HIPCHK(hipMemcpyAsync(&out_ints[(rows - 1) * SCT_TS_NI + SCT_TS_I_NAME], &ctl->last_mapped, sizeof(int64_t),
+                        hipMemcpyDeviceToDevice, s));
+  if (n > 0) {
+    const unsigned slot_blocks = (unsigned)(L.slots / kBlock);
+    if (cell) {
+      LAUNCH_N("ts_records", n, (k_ts_records<true>), dim3(rec_blocks), dim3(kBlock), s, *rec, n, first_drop,
+               third_is_mito, ent, row_start, ft, kt, xv, out_ints);
+    } else {
+      LAUNCH_N("ts_records", n, (k_ts_records<false>), dim3(rec_blocks), dim3(kBlock), s, *rec, n, first_drop,
+               third_is_mito, ent, row_start, ft, kt, xv, out_ints);
+    }
+    LAUNCH_N("ts_frag_slots", L.slots, k_ts_frag_slots, dim3(slot_blocks), dim3(kBlock), s, *rec, ent, ft, out_ints);
+    if (cell) {
+      LAUNCH_N("ts_k1_slots", L.slots, (k_ts_k1_slots<true>), dim3(slot_blocks), dim3(kBlock), s, *rec, third_is_mito,
+               ent, kt, out_ints);
+    } else {
+      LAUNCH_N("ts_k1_slots", L.slots, (k_ts_k1_slots<false>), dim3(slot_blocks), dim3(kBlock), s, *rec, third_is_mito,
+               ent, kt, out_ints);
+    }
+    LAUNCH_N("ts_chains", n, k_ts_chains, dim3((unsigned)rows), dim3(kWave), s, (const uint4*)xv, n, rows,
+             (const int32_t*)row_start, out_sums);
+  }
+  HIPCHK(hipStreamSynchronize(s));
   return SCT_OK;
 }
 

@@ -214,6 +214,39 @@ class Engine:
                                          _ffi.stream(self.device)))
         return int(out.value)
 
+    # ---- native TagSort metrics (fastqpreprocessing metricgatherer.cpp; csrc/tsmetrics.h) ----
+    def tagsort_metrics(self, cols, dims: Dims, metric_type: str, first_drop: torch.Tensor,
+                        third_is_mito: Optional[torch.Tensor] = None, capacity: Optional[int] = None):
+        """The native gatherer's rows of records sorted by (first, second, third) tag rank, held in the
+        ``cell`` / ``umi`` / ``gene`` columns in that position (sct_tagsort_metrics): (ints [rows, 21] int64,
+        sums [rows, 12] float64: count, sum, sum of squares per stream) on the device.  ``capacity`` is a
+        first guess of the row count; the call is repeated once with the exact count when it is too small."""
+        if metric_type not in ("cell", "gene"):
+            raise ValueError("metric_type must be 'cell' or 'gene'")
+        rec = records_struct(cols)
+        n = int(rec.n)
+        cap = min(n + 1, int(capacity) if capacity else 2 * int(dims.n_cell_ids) + 1024)
+        ptr = (lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None)
+        for _ in range(2):
+            plan = self._plan(n, metric_type, "exact", dims, max_entities=cap)
+            nbytes = ctypes.c_size_t(0)
+            N.check(self.lib.sct_tagsort_metrics_workspace_size(ctypes.byref(plan), ctypes.byref(nbytes)))
+            ws = torch.empty(max(1, int(nbytes.value)), dtype=torch.uint8, device=self.device)
+            ints = torch.empty((cap, N.SCT_TS_NI), dtype=torch.int64, device=self.device)
+            sums = torch.empty((cap, N.SCT_TS_NF), dtype=torch.float64, device=self.device)
+            rows = ctypes.c_int64(0)
+            rc = self.lib.sct_tagsort_metrics(ctypes.byref(plan), ctypes.byref(rec), ptr(first_drop), ptr(third_is_mito),
+                                              ctypes.c_void_p(ws.data_ptr()), ws.numel(), ptr(ints), ptr(sums),
+                                              ctypes.byref(rows), _ffi.stream(self.device))
+            del ws
+            if rc == N.SCT_ENOMEM and int(rows.value) > cap:
+                cap = int(rows.value)
+                continue
+            N.check(rc)
+            r = int(rows.value)
+            return ints[:r], sums[:r]
+        raise N.EngineError("sct_tagsort_metrics: the row count changed between two calls")
+
     # ---- cell bins exchanged between devices (SplitBam's bins, bam.py:439-480; exchange.h) ----
     def bin_records(self, cols, dims: Dims, n_bins: int, tiebreak: Optional[torch.Tensor] = None,
                     bin_of_cell: Optional[torch.Tensor] = None):

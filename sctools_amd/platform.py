@@ -30,6 +30,11 @@ From the reference's fastqpreprocessing tools: ``FastqMetrics --R1 FASTQ [--R1 F
 [--num-shards N] [--output-dir DIR] [--device N]`` (``fastqprocess.cpp``, ``fastq_slideseq.cpp``;
 ``sctools_amd/fastq_process.py``); ``FastqSlideseq`` is the same command.
 
+``TagSort --bam-input BAM --metric-type cell|gene --compute-metric --metric-output CSV --barcode-tag T
+--umi-tag T --gene-tag T (their order is the sort order) [--gtf-file GTF] [--mitochondrial-gene-names-filename FILE]
+[--temp-folder DIR] [--alignments-per-thread N] [--nthreads N] [--device N]`` (``tagsort.cpp``,
+``metricgatherer.cpp``; ``sctools_amd/tagsort.py``).
+
 New flags are optional only: ``--float-mode {welford,exact}``, ``--device``, ``--devices N``
 (spread the entity runs over GPUs 0..N-1, one host thread each; same output) and, on
 CalculateCellMetrics, ``--gene-output-filestem STEM`` (also write the gene rows of the same
@@ -285,6 +290,14 @@ class GenericPlatform:
                  100.0 * result.n_uncorrectable / max(result.n_reads, 1)))
         return 0
 
+    @classmethod
+    def tag_sort(cls, args: Iterable[str] = None) -> int:
+        """TagSort (the reference's fastqpreprocessing ``TagSort`` binary): the unsorted BAM ordered by three
+        tags and the cell or gene metrics of the sorted reads, gathered on the GPU; one CSV."""
+        from sctools_amd import tagsort
+
+        return tagsort.main(args)
+
 
 class TenXV2(GenericPlatform):
     """10x Genomics v2: the metric commands (platform.py:579) and ``Attach10xBarcodes``.
@@ -456,4 +469,5 @@ COMMANDS = {
     "FastqMetrics": GenericPlatform.fastq_metrics,
     "FastqProcess": GenericPlatform.fastq_process,
     "FastqSlideseq": GenericPlatform.fastq_process,
+    "TagSort": GenericPlatform.tag_sort,
 }
