@@ -79,7 +79,21 @@ int sct_gbam_parse(sct_gbam_t* h, int32_t metric_mode, void* const* columns);
  * Returns SCT_BAM_OK, SCT_GBAM_HOST, or SCT_BAM_EIO on a device error. */
 int sct_gbam_parse_count(sct_gbam_t* h, const char* tags, void* const* columns);
 
-/* The ranked dictionary `which` (SCT_BAM_TAG_CB / _UB / _GE) after sct_gbam_parse(_count), as
+/* Phase 2, TagSort mode (sct_bam.h SCT_BAM_TAGSORT; the per-read stage of the reference's native
+ * TagSort, fastqpreprocessing/src/htslib_tagsort.cpp:106-218): `tags` holds the barcode, umi and
+ * gene tag names (6 characters, as sct_gbam_parse_count); columns: the fourteen of sct_gbam_parse,
+ * in its order.  A tag's first occurrence is read (bam_aux_get); a missing named tag and the value
+ * "-" are the missing id; CR / CY / UR / UY / XF of another type than Z / H count as missing;
+ * perfect barcodes are strcmp(tag or "None", raw or ""); CY counts (uint8_t)(c - 33) > 30 and UY
+ * (int)c - 33 > 30; unmapped is refID == -1; NH1 needs an integer NH; the quality columns cover all
+ * l_seq quality bytes; lengths of 0 are kept and nothing is validated.  A named tag of another type
+ * than Z / H, a record past the columns' width (l_seq or the quality sum above 65535, a CY / UY
+ * longer than 255), a malformed tag area and non-ASCII or over-long named values return
+ * SCT_GBAM_HOST (the host decoder raises the error or decodes the file).
+ * Returns SCT_BAM_OK, SCT_GBAM_HOST, or SCT_BAM_EIO on a NULL argument or a device error. */
+int sct_gbam_parse_tagsort(sct_gbam_t* h, const char* tags, void* const* columns);
+
+/* The ranked dictionary `which` (SCT_BAM_TAG_CB / _UB / _GE) after sct_gbam_parse(_count, _tagsort), as
  * sct_bam_dictionary: *n names, names[i] = bytes[offsets[i] .. offsets[i+1]), entry 0 the
  * missing tag when *has_none.  Valid until sct_gbam_close. */
 int sct_gbam_dictionary(const sct_gbam_t* h, int32_t which, int64_t* n, const char** bytes,

@@ -12,7 +12,9 @@
 //   4. k_parse: one lane per record -- the validation and fields of bamdec.cpp parse_record
 //      (sct_bam.h), and CB / UB / GE interned in open-addressing tables (one 64-bit CAS per
 //      insert: the string's offset in U, its length and 16 hash bits); k_parse_count: the
-//      count-matrix mode (three named tags, XF, the query-name group head);
+//      count-matrix mode (three named tags, XF, the query-name group head); k_parse_tagsort: the
+//      native TagSort's per-read rule (bamdec.cpp parse_tagsort_record), the whole-read quality
+//      sums taken by 16 lanes per record;
 //   5. per dictionary the occupied slots are compacted, the distinct strings packed and copied to
 //      the host, sorted there (Python's sorted() order, the missing tag first) and the rank of
 //      every slot copied back; k_remap turns slot ids into ranks.
@@ -603,6 +605,184 @@ __global__ void k_parse_count(const uint8_t* __restrict__ U, const uint64_t* __r
     if (host) break;
     C.cell[r] = id0, C.umi[r] = id1, C.gene[r] = id2;
     C.xf[r] = (uint8_t)x, C.qhead[r] = (uint8_t)head;
+  } while (false);
+  if (host) atomicOr(&flags[0], 1u);
+}
+
+// TagSort mode (bamdec.cpp parse_tagsort_record; htslib_tagsort.cpp:106-218).  A tag's FIRST
+// occurrence (bam_aux_get), kept as an offset from the record's data: st 0 not seen, 1 a Z / H
+// string, 2 any other type (get_Ztag_or_default then reads it as missing).
+struct TsTag {
+  uint32_t off, n, st;
+};
+__device__ __forceinline__ void ts_first(TsTag& dst, uint32_t off, uint32_t n, uint32_t st) {
+  if (!dst.st) dst.off = off, dst.n = n, dst.st = st;
+}
+// a string tag as get_Ztag_or_default gives it: another type and the value "-" are the default
+__device__ __forceinline__ bool ts_present(const uint8_t* U, uint64_t d, const TsTag& v) {
+  return v.st == 1 && !(v.n == 1 && U[d + v.off] == '-');
+}
+// strcmp(tag or "None", raw or "") == 0 (a Z value holds no NUL, so its length is its strlen)
+__device__ __forceinline__ bool ts_perfect(const uint8_t* U, uint64_t d, bool has_tag, const TsTag& tag, bool has_raw,
+                                           const TsTag& raw) {
+  const uint32_t an = has_tag ? tag.n : 4, bn = has_raw ? raw.n : 0;
+  if (an != bn) return false;
+  if (has_tag) return str_eq(U, d + tag.off, d + raw.off, bn);
+  const char none[4] = {'N', 'o', 'n', 'e'};
+  for (uint32_t k = 0; k < bn; k++)
+    if (U[d + raw.off + k] != (uint8_t)none[k]) return false;
+  return true;
+}
+
+// Whole-read quality sums, 16 lanes per record: lane group g (lanes 16g .. 16g + 15 of the wave)
+// takes the records of its own 16 lanes one after the other, every lane one aligned 8-byte word of
+// the quality bytes [q0, q0 + len) per step (U is a hipMalloc pointer, so a payload offset that is
+// a multiple of 8 is an aligned address).  The bytes of a word outside the range are masked off;
+// a word reaching past the resident payload (ulen) is not loaded: its bytes before ulen are read
+// one by one.  All 64 lanes call it (len 0: nothing to read); lane l returns its own record's
+// sum and count of bytes > 30.
+__device__ __forceinline__ void ts_quality(const uint8_t* __restrict__ U, uint64_t ulen, uint64_t qoff, uint32_t qlen,
+                                           uint32_t* sum, uint32_t* gt30) {
+  const uint32_t sub = threadIdx.x & 15;
+  uint32_t my_s = 0, my_g = 0;
+  for (uint32_t it = 0; it < 16; it++) {
+    const uint32_t lo = __shfl((uint32_t)qoff, (int)it, 16), hi = __shfl((uint32_t)(qoff >> 32), (int)it, 16);
+    const uint32_t len = __shfl(qlen, (int)it, 16);
+    const uint64_t q0 = (uint64_t)hi << 32 | lo, q1 = q0 + len;
+    uint32_t s = 0, g = 0;
+    for (uint64_t w = (q0 & ~7ull) + 8ull * sub; w < q1; w += 128) {
+      uint64_t x = 0;
+      if (w + 8 <= ulen) {
+        x = *reinterpret_cast<const uint64_t*>(U + w);
+      } else {
+        for (uint32_t j = 0; j < 8 && w + j < ulen; j++) x |= (uint64_t)U[w + j] << (8 * j);
+      }
+      const uint32_t a = q0 > w ? (uint32_t)(q0 - w) : 0;       // first byte of the word in range: 0..7
+      const uint32_t b = q1 - w < 8 ? (uint32_t)(q1 - w) : 8;   // one past the last: 1..8
+      uint64_t m = ~0ull << (8 * a);
+      if (b < 8) m &= (1ull << (8 * b)) - 1;
+      x &= m;
+      s = __builtin_amdgcn_sad_u8((uint32_t)x, 0u, s);
+      s = __builtin_amdgcn_sad_u8((uint32_t)(x >> 32), 0u, s);
+      // byte > 30: bit 7 of (low seven bits + 97), or the byte's own bit 7
+      const uint64_t t = (((x & 0x7f7f7f7f7f7f7f7full) + 0x6161616161616161ull) | x) & 0x8080808080808080ull;
+      g += __popcll(t);
+    }
+    for (int o = 8; o > 0; o >>= 1) {
+      s += __shfl_xor(s, o, 16);
+      g += __shfl_xor(g, o, 16);
+    }
+    if (sub == it) my_s = s, my_g = g;
+  }
+  *sum = my_s, *gt30 = my_g;
+}
+
+// One lane per record's tags and fields, 16 lanes per record's qualities.  tcb / tub / tge: the
+// barcode, umi and gene tag names as (a << 8 | b); ulen: the resident payload's length.  Every
+// record agrees with parse_tagsort_record or sets flags[0] (the host decoder takes the file).
+__global__ void k_parse_tagsort(const uint8_t* __restrict__ U, uint64_t ulen, const uint64_t* __restrict__ starts,
+                                uint64_t n, uint32_t tcb, uint32_t tub, uint32_t tge, Cols C, Dicts D,
+                                uint32_t* __restrict__ flags) {
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool host = false, ok = false;
+  uint64_t d = 0, qual = 0, end = 0;
+  uint32_t l_seq = 0;
+  if (r < n) {
+    const uint64_t p = starts[r];
+    const uint32_t bs = u32(U, p);
+    d = p + 4;
+    end = d + bs;
+    if (bs < 32) {
+      host = true;
+    } else {
+      l_seq = u32(U, d + 16);
+      qual = d + 32 + U[d + 8] + 4ull * u16(U, d + 12) + (l_seq + 1ull) / 2;
+      // before any loop bounded by the file: the record holds what it announces, within the columns' width
+      if (qual + l_seq > end || l_seq > 0xffff) host = true;
+      else ok = true;
+    }
+  }
+  uint32_t s = 0, g = 0;
+  ts_quality(U, ulen, ok ? qual : 0, ok ? l_seq : 0, &s, &g);  // (the whole wave: no lane has left)
+  if (ok) do {
+    const int32_t ref = (int32_t)u32(U, d), pos = (int32_t)u32(U, d + 4);
+    const uint32_t n_cigar = u16(U, d + 12), flag = u16(U, d + 14);
+    const uint64_t cig = d + 32 + U[d + 8];
+    TsTag cb{}, ub{}, ge{}, cr{}, cy{}, ur{}, uy{}, xf{};
+    uint32_t nh = 0;  // 1: the first NH is an integer 1; 2: it is anything else
+    uint64_t q = qual + l_seq;
+    while (q + 3 <= end) {
+      const uint32_t ab = (uint32_t)U[q] << 8 | U[q + 1], t = U[q + 2];
+      q += 3;
+      DTag v{};
+      const uint32_t used = tag_value(U, q, end, t, &v);
+      if (!used) { host = true; break; }
+      const uint32_t off = (uint32_t)(q - d), st = t == 'Z' || t == 'H' ? 1 : 2;
+      q += used;
+      // each role on its own: a named tag may itself be CR or UR
+      if (ab == tcb) ts_first(cb, off, v.n, st);
+      if (ab == tub) ts_first(ub, off, v.n, st);
+      if (ab == tge) ts_first(ge, off, v.n, st);
+      if (ab == ('C' << 8 | 'R')) ts_first(cr, off, v.n, st);
+      if (ab == ('C' << 8 | 'Y')) ts_first(cy, off, v.n, st);
+      if (ab == ('U' << 8 | 'R')) ts_first(ur, off, v.n, st);
+      if (ab == ('U' << 8 | 'Y')) ts_first(uy, off, v.n, st);
+      if (ab == ('X' << 8 | 'F')) ts_first(xf, off, v.n, st);
+      if (ab == ('N' << 8 | 'H') && !nh) nh = v.kind == TV_INT && v.i == 1 ? 1 : 2;
+    }
+    if (host) break;
+    if (cb.st == 2 || ub.st == 2 || ge.st == 2) { host = true; break; }  // bam_aux2Z of a typed value: the host's ETYPED
+    const bool has_cb = ts_present(U, d, cb), has_ub = ts_present(U, d, ub), has_ge = ts_present(U, d, ge);
+    const bool has_cr = ts_present(U, d, cr), has_ur = ts_present(U, d, ur);
+    uint32_t bits = 0, cg = 0, cl = 0, ug = 0, ul = 0;
+    if (has_cb) bits |= B_HAS_CB;
+    if (ts_perfect(U, d, has_cb, cb, has_cr, cr)) bits |= B_PERFECT_CB;
+    if (ts_perfect(U, d, has_ub, ub, has_ur, ur)) bits |= B_PERFECT_UMI;
+    if (ts_present(U, d, cy)) {
+      cl = cy.n;
+      if (cl > 0xff) { host = true; break; }
+      for (uint32_t k = 0; k < cl; k++) cg += (uint8_t)(U[d + cy.off + k] - 33) > 30;  // uint8_t: below 33 wraps
+    }
+    if (ts_present(U, d, uy)) {
+      ul = uy.n;
+      if (ul > 0xff) { host = true; break; }
+      for (uint32_t k = 0; k < ul; k++) ug += (int)U[d + uy.off + k] - 33 > 30;  // int: below 33 does not count
+    }
+    uint32_t x = XF_ABSENT;
+    if (ts_present(U, d, xf) && xf.n > 0) {
+      DTag v{};
+      v.off = d + xf.off, v.n = xf.n;
+      x = XF_OTHER;
+      if (lit_eq(U, v, "CODING", 6)) x = XF_CODING;
+      else if (lit_eq(U, v, "INTRONIC", 8)) x = XF_INTRONIC;
+      else if (lit_eq(U, v, "UTR", 3)) x = XF_UTR;
+      else if (lit_eq(U, v, "INTERGENIC", 10)) x = XF_INTERGENIC;
+    }
+    if (ref == -1) bits |= B_UNMAPPED;  // (the flag's 0x4 is not read)
+    if (nh == 1) bits |= B_NH1;
+    for (uint32_t k = 0; k < n_cigar; k++) {
+      const uint32_t c = u32(U, cig + 4ull * k);
+      if ((c & 0xf) == 3 && (c >> 4) != 0) {
+        bits |= B_SPLICED;
+        break;
+      }
+    }
+    if (flag & 0x10) bits |= B_REVERSE;
+    if (flag & 0x400) bits |= B_DUPLICATE;
+    if (s > 0xffff) { host = true; break; }
+    int32_t id0 = -1, id1 = -1, id2 = -1;
+    if (has_cb) host |= (id0 = intern(D, 0, U, d + cb.off, cb.n)) < 0;
+    else atomicOr(&flags[1], 1u);
+    if (has_ub) host |= (id1 = intern(D, 1, U, d + ub.off, ub.n)) < 0;
+    else atomicOr(&flags[2], 1u);
+    if (has_ge) host |= (id2 = intern(D, 2, U, d + ge.off, ge.n)) < 0;
+    else atomicOr(&flags[3], 1u);
+    if (host) break;
+    C.cell[r] = id0, C.umi[r] = id1, C.gene[r] = id2;
+    C.ref[r] = ref, C.pos[r] = pos;
+    C.gq_sum[r] = (uint16_t)s, C.gq_len[r] = (uint16_t)l_seq, C.gq_gt30[r] = (uint16_t)g;
+    C.bits[r] = (uint8_t)bits, C.xf[r] = (uint8_t)x;
+    C.cy_gt30[r] = (uint8_t)cg, C.cy_len[r] = (uint8_t)cl, C.uy_gt30[r] = (uint8_t)ug, C.uy_len[r] = (uint8_t)ul;
   } while (false);
   if (host) atomicOr(&flags[0], 1u);
 }
@@ -1618,6 +1798,31 @@ int parse_count_impl(sct_gbam* G, const char* tags, void* const* cols) {
   return dictionaries_impl(G, P, colk);
 }
 
+int parse_tagsort_impl(sct_gbam* G, const char* tags, void* const* cols) {
+  ParseState P;
+  int rc = parse_begin(G, P);
+  if (rc) return rc;
+  Cols C;
+  C.cell = (int32_t*)cols[0], C.umi = (int32_t*)cols[1], C.gene = (int32_t*)cols[2];
+  C.ref = (int32_t*)cols[3], C.pos = (int32_t*)cols[4];
+  C.gq_sum = (uint16_t*)cols[5], C.gq_len = (uint16_t*)cols[6], C.gq_gt30 = (uint16_t*)cols[7];
+  C.bits = (uint8_t*)cols[8], C.xf = (uint8_t*)cols[9], C.cy_gt30 = (uint8_t*)cols[10];
+  C.cy_len = (uint8_t*)cols[11], C.uy_gt30 = (uint8_t*)cols[12], C.uy_len = (uint8_t*)cols[13];
+  auto tag = [&](int k) { return (uint32_t)(uint8_t)tags[2 * k] << 8 | (uint8_t)tags[2 * k + 1]; };
+  int32_t* const colk[3] = {C.cell, C.umi, C.gene};
+  rc = parse_windows(G, P, colk, [&](const WinInfo& w, const uint64_t* starts, uint64_t n, bool) {
+    Cols Cw = C;
+    const uint64_t b = w.base;
+    Cw.cell += b, Cw.umi += b, Cw.gene += b, Cw.ref += b, Cw.pos += b;
+    Cw.gq_sum += b, Cw.gq_len += b, Cw.gq_gt30 += b, Cw.bits += b, Cw.xf += b;
+    Cw.cy_gt30 += b, Cw.cy_len += b, Cw.uy_gt30 += b, Cw.uy_len += b;
+    hipLaunchKernelGGL(k_parse_tagsort, dim3(grid(n, 256)), dim3(256), 0, G->st, G->u.p, w.ulen, starts, n, tag(0),
+                       tag(1), tag(2), Cw, P.D, P.flags.p);
+  });
+  if (rc) return rc;
+  return dictionaries_impl(G, P, colk);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1745,6 +1950,17 @@ int sct_gbam_parse_count(sct_gbam_t* h, const char* tags, void* const* columns) 
     if (!columns[k]) return gfail(SCT_BAM_EIO, "NULL column");
   DeviceGuard guard;
   return parse_count_impl(h, tags, columns);
+}
+
+int sct_gbam_parse_tagsort(sct_gbam_t* h, const char* tags, void* const* columns) {
+  g_gerr.clear();
+  if (!h || !tags || !columns) return gfail(SCT_BAM_EIO, "NULL argument");
+  for (int k = 0; k < 6; k++)
+    if (!tags[k]) return gfail(SCT_BAM_EIO, "tags: six characters (barcode, umi, gene tag names)");
+  for (int k = 0; k < 14; k++)
+    if (!columns[k]) return gfail(SCT_BAM_EIO, "NULL column");
+  DeviceGuard guard;
+  return parse_tagsort_impl(h, tags, columns);
 }
 
 int sct_gbam_dictionary(const sct_gbam_t* h, int32_t which, int64_t* n, const char** bytes, const int64_t** offsets,

@@ -8,7 +8,8 @@ dictionary strings visit the host (to be ranked in Python's ``sorted()`` order).
 
 It stands in for the same reference reads as ``bamnative`` (the per-record pysam loop of
 ``MetricAggregator.parse_molecule``, ``aggregator.py:251-334``, and
-``CellMetrics.parse_extra_fields``, ``aggregator.py:507-530``).  A file the device path does not
+``CellMetrics.parse_extra_fields``, ``aggregator.py:507-530``; in "tagsort" mode the per-read stage of the native TagSort,
+``htslib_tagsort.cpp:106-218``).  A file the device path does not
 reproduce exactly (a record the reference rejects, typed dictionary tags, non-ASCII dictionary
 bytes, a malformed deflate stream, an empty file) returns ``None``: the caller decodes it with
 ``bamnative``, whose error is the reference's exception for the first offending record.
@@ -37,6 +38,7 @@ PROTOTYPES = {
     "sct_gbam_remap": (_int, [_vp, _P(_i32), _i64, _vp, _i64]),
     "sct_gbam_parse": (_int, [_vp, _i32, _P(_vp)]),
     "sct_gbam_parse_count": (_int, [_vp, ctypes.c_char_p, _P(_vp)]),
+    "sct_gbam_parse_tagsort": (_int, [_vp, ctypes.c_char_p, _P(_vp)]),
     "sct_gbam_dictionary": (_int, [_vp, _i32, _P(_i64), _P(_vp), _P(_vp), _P(_i32)]),
     "sct_gbam_read_inflated": (_int, [_vp, _u64, _u64, _vp, _P(_u64)]),
     "sct_gbam_timing": (_int, [_vp, _P(ctypes.c_double)]),
@@ -111,7 +113,11 @@ def decode(path: str, metric_mode: str = "cell", device=None, timings: Optional[
     each dictionary is a ``columnar.PackedDictionary`` (strings decoded only when asked for).
 
     ``metric_mode`` "count": the count-matrix columns ``COUNT_COLUMNS`` of the three tags named by
-    ``tags`` (cell, molecule, gene), as ``bamnative.decode(path, "count", tags=tags)``."""
+    ``tags`` (cell, molecule, gene), as ``bamnative.decode(path, "count", tags=tags)``.
+
+    ``metric_mode`` "tagsort": the record columns under the native TagSort's per-read rule for the
+    three tags named by ``tags`` (barcode, umi, gene), as ``bamnative.decode(path, "tagsort",
+    tags=tags)``."""
     import torch
 
     from sctools_amd import _native as N
@@ -122,8 +128,8 @@ def decode(path: str, metric_mode: str = "cell", device=None, timings: Optional[
         H.check_open()
         if H.rc == HOST:
             return None
-        if metric_mode == "count" and (tags is None or len(tags) != 3 or any(len(t) != 2 for t in tags)):
-            raise ValueError("count mode needs three 2-character tag names")
+        if metric_mode in ("count", "tagsort") and (tags is None or len(tags) != 3 or any(len(t) != 2 for t in tags)):
+            raise ValueError("%s mode needs three 2-character tag names" % metric_mode)
         names_ = COUNT_COLUMNS if metric_mode == "count" else N.RECORD_COLUMNS
         try:  # columns that do not fit the device: the host decoder takes the file
             if metric_mode == "count":
@@ -136,6 +142,8 @@ def decode(path: str, metric_mode: str = "cell", device=None, timings: Optional[
         ptrs = (ctypes.c_void_p * len(names_))(*[cols[c].data_ptr() for c in names_])
         if metric_mode == "count":
             rc = H.L.sct_gbam_parse_count(H.h, "".join(tags).encode("ascii"), ptrs)
+        elif metric_mode == "tagsort":
+            rc = H.L.sct_gbam_parse_tagsort(H.h, "".join(tags).encode("ascii"), ptrs)
         else:
             rc = H.L.sct_gbam_parse(H.h, _MODES[metric_mode], ptrs)
         _check(rc)

@@ -32,7 +32,7 @@ From the reference's fastqpreprocessing tools: ``FastqMetrics --R1 FASTQ [--R1 F
 
 ``TagSort --bam-input BAM --metric-type cell|gene --compute-metric --metric-output CSV --barcode-tag T
 --umi-tag T --gene-tag T (their order is the sort order) [--gtf-file GTF] [--mitochondrial-gene-names-filename FILE]
-[--temp-folder DIR] [--alignments-per-thread N] [--nthreads N] [--device N]`` (``tagsort.cpp``,
+[--temp-folder DIR] [--alignments-per-thread N] [--nthreads N] [--device N] [--decoder auto|host]`` (``tagsort.cpp``,
 ``metricgatherer.cpp``; ``sctools_amd/tagsort.py``).
 
 New flags are optional only: ``--float-mode {welford,exact}``, ``--device``, ``--devices N``

@@ -1,6 +1,7 @@
 """End-to-end drop-in timing: GatherCellMetrics on a BAM (decode -> GPU metrics -> CSV.gz).
 
 python tools/e2e_bench.py [--records N] [--bam PATH] [--host-decoder]   (needs a GPU)
+python tools/e2e_bench.py --tagsort [--metric-type cell|gene] [--host-decoder]   (TagSort.run on the same BAM)
 
 The BAM is the reference's small-cell-sorted.bam payload (656 records of 58 cells) replicated
 until it holds N records, every group of --replicas-per-cell consecutive replicas given one cell
@@ -158,11 +159,17 @@ def main():
                     help="also time GatherCellMetrics(devices=[0] * N): N parts decoded and computed together")
     ap.add_argument("--count", action="store_true",
                     help="CountMatrix.from_sorted_tagged_bam (CreateCountMatrix) on the cell-sorted BAM instead")
+    ap.add_argument("--tagsort", action="store_true",
+                    help="TagSort(...).run() (the native TagSort: decode, sort, gatherer, CSV) on the cell-sorted "
+                         "BAM instead, tags CB UB GE in that order")
+    ap.add_argument("--metric-type", default="cell", choices=["cell", "gene"], help="the metrics of --tagsort")
     a = ap.parse_args()
     if a.gene:
         return main_gene(a)
     if a.count:
         return main_count(a)
+    if a.tagsort:
+        return main_tagsort(a)
     bam = a.bam or ("/tmp/sct_synth_%d.bam" if a.synth else "/tmp/sct_e2e_%d.bam") % a.records
     if not os.path.exists(bam) and a.synth:
         t0 = time.time()
@@ -337,6 +344,66 @@ def main_count(a):
         res["device_and_host_decoder_identical"] = bool(
             m.matrix.shape == h.matrix.shape and (m.matrix != h.matrix).nnz == 0
             and np.array_equal(m.row_index, h.row_index))
+    print(json.dumps(res))
+
+
+def main_tagsort(a):
+    """TagSort end to end: device decode (tagsort mode) + sort + gatherer + CSV as one ``run()`` call,
+    against the same call with the host decoder; the GTF and the mitochondrial names are the
+    tagsort_native fixture's."""
+    bam = a.bam or "/tmp/sct_e2e_%d.bam" % a.records
+    if not os.path.exists(bam):
+        make_bam(bam, a.records, a.replicas_per_cell)
+    import torch
+
+    from sctools_amd import tagsort as T
+
+    torch.cuda.init()
+    with open(bam, "rb") as f:
+        while f.read(1 << 26):
+            pass
+    fixtures = os.path.join(ROOT, "tests", "golden", "tagsort_native")
+    kw = {"tag_order": ("gene", "barcode", "umi")}  # gene rows: the gene tag sorts first
+    if a.metric_type == "cell":
+        kw = {"tag_order": T.ROLES, "gtf_file": os.path.join(fixtures, "genes.gtf"),
+              "mitochondrial_gene_names_filename": os.path.join(fixtures, "mito_names.txt")}
+
+    def job(decoder):
+        return T.TagSort(bam, a.metric_type, "CB", "UB", "GE", decoder=decoder, **kw)
+
+    out = "/tmp/sct_e2e_tagsort_%s" % a.metric_type
+    # warm-up, and the stages of one run taken apart
+    ts, tm = job("auto"), {}
+    t0 = time.perf_counter()
+    ranked = ts.decode(tm)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    n = int(ranked.columns["cell"].shape[0])
+    rows = T.gather(ranked, a.metric_type)
+    t2 = time.perf_counter()
+    T.write_metrics(rows, out + ".warm.csv")
+    t3 = time.perf_counter()
+    res = {"bam": bam, "bam_mb": os.path.getsize(bam) / 1e6, "entry": "TagSort.run", "metric_type": a.metric_type,
+           "tag_order": list(kw["tag_order"]), "records": n, "rows": len(rows), "decoded_by": ts.decoded_by, "decode_s": t1 - t0,
+           "device_decode_stages_s": tm, "sort_gather_s": t2 - t1, "csv_s": t3 - t2}
+    del ranked, rows
+    torch.cuda.empty_cache()
+    runs = []
+    for _ in range(3):
+        ts = job("auto")
+        t0 = time.perf_counter()
+        ts.run(out + ".csv")
+        runs.append(time.perf_counter() - t0)
+    res["TagSort_s"] = runs
+    res["TagSort_records_per_s"] = n / min(runs)
+    res["decoded_by"] = ts.decoded_by
+    if a.host_decoder:
+        t0 = time.perf_counter()
+        job("host").run(out + ".host.csv")
+        res["TagSort_host_decoder_s"] = time.perf_counter() - t0
+        res["TagSort_host_decoder_records_per_s"] = n / res["TagSort_host_decoder_s"]
+        res["device_and_host_decoder_csv_identical"] = (open(out + ".csv", "rb").read() ==
+                                                        open(out + ".host.csv", "rb").read())
     print(json.dumps(res))
 
 

@@ -1,6 +1,7 @@
 """Device BAM decode timing (experiments): stages of gbam.decode on one BAM, best of --reps.
 
-python tools/gbam_time.py BAM [--reps 3]   (SCT_GBAM_LIB_PATH selects an experimental library)
+python tools/gbam_time.py BAM [--reps 3] [--mode cell|gene|tagsort] [--tags CB UB GE]
+(SCT_GBAM_LIB_PATH selects an experimental library)
 """
 import argparse
 import json
@@ -15,7 +16,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("bam")
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--mode", default="cell", choices=["cell", "gene"])
+    ap.add_argument("--mode", default="cell", choices=["cell", "gene", "tagsort"])
+    ap.add_argument("--tags", nargs=3, default=["CB", "UB", "GE"], metavar=("BARCODE", "UMI", "GENE"),
+                    help="the three tag names of --mode tagsort")
     a = ap.parse_args()
     import torch
 
@@ -27,7 +30,8 @@ def main():
     for _ in range(a.reps + 1):
         tm = {}
         t0 = time.perf_counter()
-        got = gbam.decode(a.bam, a.mode, dev, timings=tm, lazy=True)
+        got = gbam.decode(a.bam, a.mode, dev, timings=tm, lazy=True,
+                          tags=tuple(a.tags) if a.mode == "tagsort" else None)
         torch.cuda.synchronize()
         t = time.perf_counter() - t0
         if got is None:
@@ -37,7 +41,8 @@ def main():
         if best is None or t < best[0]:
             best = (t, tm, n)
     t, tm, n = best
-    print(json.dumps({"lib": gbam.LIB_PATH, "records": n, "decode_s": t, "records_per_s": n / t, "stages_s": tm}))
+    print(json.dumps({"lib": gbam.LIB_PATH, "mode": a.mode, "records": n, "decode_s": t, "records_per_s": n / t,
+                      "stages_s": tm}))
 
 
 if __name__ == "__main__":
