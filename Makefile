@@ -14,7 +14,7 @@ FASTQ := sctools_amd/libsct_fastq.so
 
 SI4 := tests/native/libsct_engine_si4.so
 
-all: $(ENGINE) $(BAMDEC) $(CSVFMT) $(GBAM) $(BARCODE) $(FASTQ) oracle/liboracle.so tests/native/libfxcheck.so tests/native/libstdhash.so tests/native/libtsround.so $(SI4)
+all: $(ENGINE) $(BAMDEC) $(CSVFMT) $(GBAM) $(BARCODE) $(FASTQ) oracle/liboracle.so tests/native/libfxcheck.so tests/native/libstdhash.so tests/native/libtsround.so tests/native/libfqcrc.so $(SI4)
 
 $(ENGINE): $(SRC) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -o $@ $(SRC) -L/opt/rocm/lib -lrccl
@@ -32,7 +32,7 @@ $(GBAM): sctools_amd/csrc/gbam.hip sctools_amd/csrc/inflate.h sctools_amd/csrc/b
 $(BARCODE): sctools_amd/csrc/barcode.hip sctools_amd/csrc/liberr.h include/sct_barcode.h
 	$(HIPCC) $(HIPFLAGS) -o $@ sctools_amd/csrc/barcode.hip
 
-$(FASTQ): sctools_amd/csrc/fastq.hip sctools_amd/csrc/fqmetrics.h sctools_amd/csrc/fqprocess.h sctools_amd/csrc/liberr.h include/sct_fastq.h include/sct_fastq_metrics.h include/sct_fastq_process.h
+$(FASTQ): sctools_amd/csrc/fastq.hip sctools_amd/csrc/fqmetrics.h sctools_amd/csrc/fqprocess.h sctools_amd/csrc/fqinflate.h sctools_amd/csrc/inflate.h sctools_amd/csrc/liberr.h include/sct_fastq.h include/sct_fastq_metrics.h include/sct_fastq_process.h include/sct_fastq_inflate.h
 	$(HIPCC) $(HIPFLAGS) -o $@ sctools_amd/csrc/fastq.hip
 
 $(CSVFMT): sctools_amd/csrc/csvfmt.cpp include/sct_csv.h
@@ -49,10 +49,14 @@ tests/native/libstdhash.so: tests/native/stdhash.cpp
 tests/native/libtsround.so: tests/native/tsround.cpp sctools_amd/csrc/tsround.h
 	g++ -O2 -std=c++17 -ffp-contract=off -fPIC -shared -o $@ tests/native/tsround.cpp
 
+# the CRC-32 of fqinflate.h (slices, fold) on the host, beside zlib's (tests/test_fastq_bgzf_cpu.py)
+tests/native/libfqcrc.so: tests/native/fqcrc.cpp sctools_amd/csrc/fqinflate.h
+	g++ -O2 -std=c++17 -fPIC -shared -Wall -o $@ tests/native/fqcrc.cpp
+
 tests/native/libfxcheck.so: tests/native/fxcheck.cpp sctools_amd/csrc/fixedpt.h
 	g++ -O2 -std=c++17 -ffp-contract=off -fPIC -shared -o $@ tests/native/fxcheck.cpp
 
 clean:
-	rm -f $(ENGINE) $(BAMDEC) $(CSVFMT) $(GBAM) $(BARCODE) $(FASTQ) oracle/liboracle.so tests/native/libfxcheck.so tests/native/libstdhash.so tests/native/libtsround.so $(SI4)
+	rm -f $(ENGINE) $(BAMDEC) $(CSVFMT) $(GBAM) $(BARCODE) $(FASTQ) oracle/liboracle.so tests/native/libfxcheck.so tests/native/libstdhash.so tests/native/libtsround.so tests/native/libfqcrc.so $(SI4)
 
 .PHONY: all clean

@@ -677,11 +677,11 @@ def _host_windows(tag_sets, batch: int = _HOST_BATCH):
         yield flush()
 
 
-def _device_windows(generator, device, max_records):
+def _device_windows(generator, device, max_records, inflate):
     """The windows of ``generator.columns()`` in the column form of :func:`_host_windows`."""
     import numpy as np
 
-    for window in generator.columns(device=device, max_records=max_records):
+    for window in generator.columns(device=device, max_records=max_records, inflate=inflate):
         out = []
         for key, values in window.items():
             if len(key) != 2:
@@ -704,13 +704,18 @@ class Tagger:
         the BAM whose records receive the tags
     device : optional
         GPU index or torch device for the generators that extract on the GPU (default: current GPU)
+    inflate : {"auto", "host"}, optional
+        who inflates those generators' BGZF-compressed FASTQ files (``fastq.TextWindows``)
     """
 
-    def __init__(self, bam_file: str, device=None) -> None:
+    def __init__(self, bam_file: str, device=None, inflate: Optional[str] = None) -> None:
         if not isinstance(bam_file, str):
             raise TypeError(f'The argument "bam_file" must be of type str, not {type(bam_file)}')
         self.bam_file = bam_file
         self.device = device
+        from sctools_amd import fastq
+
+        self.inflate = fastq.check_inflate(fastq.DEFAULT_INFLATE if inflate is None else inflate)
 
     def tag(self, output_bam_name: str, tag_generators) -> None:
         """Writes the records of ``bam_file`` to ``output_bam_name`` with the tags of every generator
@@ -726,7 +731,7 @@ class Tagger:
             sources = []
             for g in tag_generators:
                 if hasattr(g, "columns") and getattr(g, "supports_columns", True):
-                    sources.append(_device_windows(g, self.device, out.n + 1))
+                    sources.append(_device_windows(g, self.device, out.n + 1, self.inflate))
                 else:
                     sources.append(_host_windows(itertools.islice(g, out.n + 1)))
             held = [(0, [], 0)] * len(sources)  # per source: (rows, columns, rows already written)

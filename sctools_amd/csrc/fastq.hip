@@ -400,3 +400,4 @@ int sct_fq_extract(const uint8_t* text, int64_t n_bytes, int64_t n_records, cons
 
 #include "fqmetrics.h"  // the sct_fqm_* calls (include/sct_fastq_metrics.h)
 #include "fqprocess.h"  // the sct_fqp_* calls (include/sct_fastq_process.h)
+#include "fqinflate.h"  // sct_fq_bgzf_scan, sct_fq_inflate (include/sct_fastq_inflate.h)

@@ -9,6 +9,7 @@ with the same class names and constructors, and the barcode extraction on the GP
 ``EmbeddedBarcodeGenerator``                    per record, the tags of every embedded barcode
 ``BarcodeGeneratorWithCorrectedCellBarcodes``   the same, with ``CB`` where the whitelist corrects ``CR``
 ``TextWindows``, ``extract_spans``              the files' text a window at a time on the GPU; its barcode columns
+``bgzf_scan``, ``bgzf_inflate``                 a BGZF file's members; its bytes inflated on the GPU
 
 Iterated on the host, the generators yield what the reference's yield: one list of
 ``(tag, value, "Z")`` per record.  Their device method ``columns()`` yields the same values a
@@ -21,7 +22,9 @@ barcode's ``end`` raises ``ValueError`` on both paths, where the reference slice
 its newline and hands on a tag value that holds a newline.
 """
 import ctypes
+import mmap
 import os
+import zlib
 from collections import namedtuple
 from typing import Iterable, Iterator, Optional, Union
 
@@ -59,6 +62,36 @@ LIBRARY = _ffi.Library("libsct_fastq.so", "sct_fastq", "sct_fq_last_error", Fast
 LIB_PATH = LIBRARY.path
 load = LIBRARY.load
 check = LIBRARY.check
+
+# include/sct_fastq_inflate.h: the same library, a table of its own (PROTOTYPES is what sct_fastq.h declares)
+NOT_BGZF = -4
+INFLATE_SLACK = 65536
+ST_CRC = 10
+MEMBER = np.dtype([("in_off", "<u8"), ("out_off", "<u8"), ("clen", "<u4"), ("isize", "<u4")])
+INFLATE_PROTOTYPES = {
+    "sct_fq_bgzf_scan": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _P(_i64), _P(_i64)]),
+    "sct_fq_crc32": (ctypes.c_uint32, [_vp, _i64]),
+    "sct_fq_inflate_workspace_size": (_int, [_i64, _P(_sz)]),
+    "sct_fq_inflate": (_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _sz, _vp, _vp, _vp]),
+}
+INFLATE_LIBRARY = _ffi.Library("libsct_fastq.so", "sct_fastq", "sct_fq_last_error", FastqError, INFLATE_PROTOTYPES,
+                               shares=LIBRARY)
+load_inflate = INFLATE_LIBRARY.load
+
+INFLATE_MODES = ("auto", "host")
+DEFAULT_INFLATE = "auto"  # who inflates a BGZF FASTQ: the device, or ("host") Python's gzip as for every other file
+_last_error = ""
+
+
+def last_error() -> str:
+    """Why the last :func:`bgzf_inflate` returned None."""
+    return _last_error
+
+
+def check_inflate(inflate: str) -> str:
+    if inflate not in INFLATE_MODES:
+        raise ValueError("inflate must be one of %s, got %r: there is no device-only mode" % (INFLATE_MODES, inflate))
+    return inflate
 
 
 class Record:
@@ -234,6 +267,213 @@ class _ByteStream:
 Window = namedtuple("Window", ["text", "n_bytes", "n_records", "workspace", "host"])
 
 
+class _DeviceWindow(Window):
+    """A window with bytes the device inflated: ``host`` is fetched from the device on first use (before the
+    next window is asked for), and the fifth item of the tuple is None."""
+
+    def __new__(cls, text, n_bytes, n_records, workspace):
+        return super().__new__(cls, text, n_bytes, n_records, workspace, None)
+
+    @property
+    def host(self):
+        if "_host" not in self.__dict__:
+            self.__dict__["_host"] = self.text[:self.n_bytes].cpu().numpy()
+        return self.__dict__["_host"]
+
+
+def bgzf_scan(data):
+    """The BGZF members of the file image ``data`` (bytes, mmap or uint8 array), by ``sct_fq_bgzf_scan``:
+    ``(members, crcs, stopped_at, reason)`` -- a ``MEMBER`` array (``in_off`` the file offset of the deflate
+    data, ``out_off`` the payload bytes before the member), the stored CRC-32 of each, the offset behind the
+    last member and None, or ``"not BGZF at byte N"`` where the scan stopped at something else."""
+    lib = load_inflate()
+    arr = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
+    size, step = int(arr.size), 1 << 16
+    parts, crc_parts, at, out, reason = [], [], 0, 0, None
+    while True:
+        members, crcs = np.zeros(step, dtype=MEMBER), np.zeros(step, dtype=np.uint32)
+        n, stop = ctypes.c_int64(0), ctypes.c_int64(0)
+        rc = lib.sct_fq_bgzf_scan(arr.ctypes.data if size else None, size, at, step, members.ctypes.data,
+                                  crcs.ctypes.data, ctypes.byref(n), ctypes.byref(stop))
+        if rc not in (0, NOT_BGZF):
+            INFLATE_LIBRARY.check(rc)
+        k = int(n.value)
+        members = members[:k]
+        members["out_off"] += np.uint64(out)
+        parts.append(members)
+        crc_parts.append(crcs[:k])
+        if k:
+            out = int(members["out_off"][-1]) + int(members["isize"][-1])
+        at = int(stop.value)
+        if rc == NOT_BGZF:
+            reason = INFLATE_LIBRARY.last_error()
+        if rc == NOT_BGZF or at >= size:
+            return np.concatenate(parts), np.concatenate(crc_parts), at, reason
+
+
+class _HostFile:
+    """One file through ``reader.open_binary``; a last line without a newline gets one."""
+
+    kind = "host"
+
+    def __init__(self, path: str, skip: int = 0):
+        self.path = path
+        self._stream = _ByteStream([path])
+        scratch = np.empty(min(max(skip, 1), 1 << 20), dtype=np.uint8)
+        while skip > 0:  # (after the device declined the file: on to where its text was good)
+            k = self._stream.readinto(scratch[:min(skip, len(scratch))])
+            if not k:
+                break
+            skip -= k
+
+    def readinto(self, view) -> int:
+        return self._stream.readinto(view)
+
+    def close(self):
+        if self._stream._file is not None:
+            self._stream._file.close()
+
+
+class _BgzfFile:
+    """A file that is BGZF from its first byte to its last, mapped: its member table and the next member."""
+
+    kind = "device"
+
+    def __init__(self, path: str, handle, mapped, image, members, crcs):
+        self.path, self._handle, self._mapped, self.image = path, handle, mapped, image
+        self.members, self.crcs = members, crcs
+        self.n, self.at = len(members), 0
+        self.starts = members["out_off"].astype(np.int64)  # of the payload, in the file's text
+        self.ends = self.starts + members["isize"].astype(np.int64)
+        self.newline_due = False
+
+    @classmethod
+    def open(cls, path: str):
+        """``(file, None)``, or ``(None, reason)`` for a file the host path reads."""
+        handle = open(path, "rb")
+        try:
+            mapped = mmap.mmap(handle.fileno(), 0, access=mmap.ACCESS_READ)
+        except (ValueError, OSError):  # an empty file, or one that cannot be mapped
+            handle.close()
+            return None, "not mapped"
+        image = np.frombuffer(mapped, dtype=np.uint8)
+        members, crcs, _, reason = bgzf_scan(image)
+        self = cls(path, handle, mapped, image, members, crcs)
+        full = np.flatnonzero(members["isize"])
+        if reason is None and len(full):  # the file's last byte decides whether a newline follows it
+            m = members[full[-1]]
+            try:
+                tail = zlib.decompress(image[int(m["in_off"]):int(m["in_off"]) + int(m["clen"])].tobytes(), -15)
+                self.newline_due = tail[-1:] != b"\n"
+            except zlib.error as e:
+                reason = "the last member does not inflate: %s" % e
+        if reason is not None:
+            self.close()
+            return None, reason
+        return self, None
+
+    def take(self, room: int):
+        """``(m1, n_bytes)``: members ``[at, m1)`` are the longest run whose ``n_bytes`` of payload fit ``room``."""
+        if self.at >= self.n:
+            return self.at, 0
+        base = int(self.starts[self.at])
+        m1 = max(self.at, int(np.searchsorted(self.ends, base + room, side="right")))
+        return m1, (int(self.ends[m1 - 1]) - base if m1 > self.at else 0)
+
+    def compressed(self, m0: int, m1: int):
+        """File offsets ``[c0, c1)`` that hold the deflate data of members ``[m0, m1)``."""
+        last = self.members[m1 - 1]
+        return int(self.members[m0]["in_off"]), int(last["in_off"]) + int(last["clen"])
+
+    def close(self):
+        self.image = None
+        try:
+            self._mapped.close()
+        except BufferError:  # a view of the map is still alive somewhere: the collector closes it
+            pass
+        self._handle.close()
+
+
+class _Inflater:
+    """The device buffers of ``sct_fq_inflate``, grown as runs need them and reused from run to run."""
+
+    def __init__(self, dev):
+        self.dev, self.lib = dev, load_inflate()
+        self.staged = self.comp = self.table = self.work = None
+
+    @staticmethod
+    def _room(t, n: int, make):
+        return t if t is not None and t.numel() >= n else make(max(n, 1) * 5 // 4 + 64)
+
+    def run(self, source: _BgzfFile, m0: int, m1: int, text, text_off: int, summary):
+        """Queues the inflate of members ``[m0, m1)`` into ``text[text_off:]`` on the current stream; returns the
+        members' status tensor.  The pinned buffers are free again once the stream has passed the call."""
+        import torch
+
+        k = m1 - m0
+        c0, c1 = source.compressed(m0, m1)
+        c0 -= c0 & 3  # (the run's first word as the file has it, so members keep their alignment)
+        n_comp = c1 - c0
+        pin = (lambda n: torch.empty(n, dtype=torch.uint8).pin_memory())
+        gpu = (lambda n: torch.empty(n, dtype=torch.uint8, device=self.dev))
+        self.staged = self._room(self.staged, n_comp, pin)
+        self.comp = self._room(self.comp, n_comp + INFLATE_SLACK, gpu)
+        self.table = self._room(self.table, 28 * k, pin)
+        need = ctypes.c_size_t(0)
+        INFLATE_LIBRARY.check(self.lib.sct_fq_inflate_workspace_size(k, ctypes.byref(need)))
+        self.work = self._room(self.work, int(need.value) + 8, gpu)
+        self.staged.numpy()[:n_comp] = source.image[c0:c1]
+        self.comp[:n_comp].copy_(self.staged[:n_comp], non_blocking=True)
+        table = self.table.numpy()
+        members = table[:24 * k].view(MEMBER)
+        members[:] = source.members[m0:m1]
+        members["in_off"] -= np.uint64(c0)
+        members["out_off"] -= np.uint64(int(source.starts[m0]))
+        table[24 * k:28 * k].view(np.uint32)[:] = source.crcs[m0:m1]
+        status = torch.empty(max(k, 1), dtype=torch.int32, device=self.dev)
+        INFLATE_LIBRARY.check(self.lib.sct_fq_inflate(
+            _ffi.ptr(self.comp), n_comp, self.comp.numel(), self.table.data_ptr(), self.table.data_ptr() + 24 * k, k,
+            _ffi.ptr(text), text.numel(), text_off, _ffi.ptr(self.work), self.work.numel(), _ffi.ptr(status),
+            _ffi.ptr(summary), _ffi.stream(self.dev)))
+        return status[:k]
+
+
+def _status_words(status, first: int) -> str:
+    mask = 0
+    for st in np.unique(status[status != 0]):
+        mask |= 1 << int(st)
+    return "status mask 0x%x, first failed member %d" % (mask, first)
+
+
+def bgzf_inflate(path: str, device=None) -> Optional[bytes]:
+    """The inflated bytes of the BGZF file ``path`` from the device path (``sct_fq_inflate``: ``k_inflate`` and
+    the CRC kernel), or None with :func:`last_error` saying why: ``not BGZF at byte N``, or the mask of the
+    members' status codes (bit ``s`` for status ``s``; bit 10 is a CRC mismatch) and the first failed member."""
+    import torch
+
+    global _last_error
+    _last_error = ""
+    dev = _ffi.device(device)
+    source, reason = _BgzfFile.open(path)
+    if source is None:
+        _last_error = reason
+        return None
+    try:
+        with torch.cuda.device(dev):
+            total = int(source.ends[-1]) if source.n else 0
+            text = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+            summary = torch.empty(2, dtype=torch.int32, device=dev)
+            if source.n:
+                status = _Inflater(dev).run(source, 0, source.n, text, 0, summary).cpu().numpy()
+                n_bad, first = (int(x) & 0xFFFFFFFF for x in summary.cpu())
+                if n_bad or status.any():
+                    _last_error = _status_words(status, first)
+                    return None
+            return text[:total].cpu().numpy().tobytes()
+    finally:
+        source.close()
+
+
 class TextWindows:
     """The decompressed text of ``files`` as one stream, a window of whole records at a time on the device.
 
@@ -242,64 +482,158 @@ class TextWindows:
     it filled for ``sct_fq_extract`` (:func:`extract_spans`), and the same bytes on the host as a uint8
     array.  What follows a window's last complete record opens the next window; a full window without
     one whole record is doubled.  A window's tensors are overwritten when the next one is asked for.
+
+    ``inflate="auto"``: a file that is BGZF from its first byte to its last is inflated on the device
+    (``sct_fq_inflate``): whole members are copied compressed and inflated behind the carry, which moves
+    device to device; such a window's ``host`` is fetched from the device when it is first asked for.
+    Every other file, and every file with ``inflate="host"``, is read through ``reader.open_binary``.  A
+    member the device declines sends its file back to the host reader from its first byte: what that
+    raises is the error, and where it raises nothing the stream goes on from the same place on the host.
+    ``inflated_by[path]`` is ``"device"`` or ``"host"`` once the file is finished, ``declined[path]`` the
+    reason where the device had a file and gave it back.
     """
 
-    def __init__(self, files, device=None, window_bytes: int = 256 << 20):
+    def __init__(self, files, device=None, window_bytes: int = 256 << 20, inflate: str = DEFAULT_INFLATE):
         self.files = list(files)
+        self.inflate = check_inflate(inflate)
         self.device = _ffi.device(device)
         stored = sum(os.stat(f).st_size for f in self.files)
         self.cap = max(16, min(int(window_bytes), max(8 * stored + 64, 1 << 16)))
+        self.inflated_by, self.declined = {}, {}
 
-    @staticmethod
-    def _fill(view, source) -> int:
-        """Reads into ``view`` until it is full or the stream ends; returns the bytes read."""
-        got = 0
-        while got < len(view):
-            k = source.readinto(view[got:])
-            if not k:
-                break
-            got += k
-        return got
+    def _open(self, path: str):
+        if self.inflate == "auto":
+            source, _ = _BgzfFile.open(path)
+            if source is not None:
+                return source
+        return _HostFile(path)
 
     def __iter__(self):
         import torch
 
         lib, dev, cap = load(), self.device, self.cap
-        source = _ByteStream(self.files)
+        pending, cur, eof = list(self.files), None, False
         with torch.cuda.device(dev):
             host = torch.empty(cap, dtype=torch.uint8).pin_memory()
             text = torch.empty(cap, dtype=torch.uint8, device=dev)
-            result = torch.empty(4, dtype=torch.int64, device=dev)
+            result = torch.empty(5, dtype=torch.int64, device=dev)  # sct_fq_result_t, then the inflate's two words
+            summary = result[4:].view(torch.int32)
+            inflater = None
             fill = 0
-            while True:
-                view = host.numpy()
-                n_bytes = fill + self._fill(view[fill:cap], source)
-                eof = source.ended
-                nbytes = ctypes.c_size_t(0)
-                check(lib.sct_fq_workspace_size(n_bytes, ctypes.byref(nbytes)))
-                work = torch.empty(int(nbytes.value) + 8, dtype=torch.uint8, device=dev)
-                text[:n_bytes].copy_(host[:n_bytes], non_blocking=True)
-                check(lib.sct_fq_count(_ffi.ptr(text), n_bytes, 1 if eof else 0, _ffi.ptr(work), work.numel(),
-                                       _ffi.ptr(result), _ffi.stream(dev)))
-                n, consumed = (int(x) for x in result[:2].cpu())
-                if n == 0:
+            # the carry text[:fill] is on the host (view[:fill]), on the device, or both
+            host_valid = dev_valid = True
+            try:
+                while True:
+                    view = host.numpy()
+                    pos, was_valid, chunk, progressed = fill, host_valid, None, False
+                    ranges = [] if dev_valid or not fill else [(0, fill)]  # of `view`, to be copied to `text`
+                    while not eof and chunk is None:
+                        if cur is None:
+                            if not pending:
+                                eof = True
+                                break
+                            cur = self._open(pending.pop(0))
+                        if cur.kind == "host":
+                            k = cur.readinto(view[pos:cap]) if pos < cap else -1
+                            if k < 0:
+                                break  # the window is full
+                            if k:
+                                if ranges and ranges[-1][1] == pos:
+                                    ranges[-1] = (ranges[-1][0], pos + k)
+                                else:
+                                    ranges.append((pos, pos + k))
+                                pos += k
+                            else:
+                                self.inflated_by[cur.path] = "host"
+                                cur.close()
+                                cur = None
+                            progressed = True
+                        elif cur.at < cur.n:
+                            m1, k = cur.take(cap - pos)
+                            if m1 == cur.at:
+                                break  # the next member does not fit behind what the window holds
+                            inflater = inflater or _Inflater(dev)
+                            status = inflater.run(cur, cur.at, m1, text, pos, summary)
+                            chunk = (cur.at, pos, int(cur.starts[cur.at]), status)
+                            cur.at = m1
+                            pos += k
+                            host_valid = False
+                            progressed = True  # (a run of empty members is progress too)
+                        elif cur.newline_due:
+                            if pos == cap:
+                                break
+                            view[pos] = 10
+                            ranges.append((pos, pos + 1))
+                            pos += 1
+                            cur.newline_due = False
+                            progressed = True
+                        else:
+                            self.inflated_by[cur.path] = "device"
+                            cur.close()
+                            cur = None
+                            progressed = True
+                    n_bytes = pos
+                    nbytes = ctypes.c_size_t(0)
+                    check(lib.sct_fq_workspace_size(n_bytes, ctypes.byref(nbytes)))
+                    work = torch.empty(int(nbytes.value) + 8, dtype=torch.uint8, device=dev)
+                    if host_valid:
+                        text[:n_bytes].copy_(host[:n_bytes], non_blocking=True)
+                    else:
+                        for a, b in ranges:
+                            text[a:b].copy_(host[a:b], non_blocking=True)
+                    dev_valid = True
+                    check(lib.sct_fq_count(_ffi.ptr(text), n_bytes, 1 if eof else 0, _ffi.ptr(work), work.numel(),
+                                           _ffi.ptr(result), _ffi.stream(dev)))
+                    fetched = [int(x) for x in result.cpu()]  # the one wait of the window: count and summary
+                    n, consumed = fetched[:2]
+                    if chunk is not None and fetched[4] & 0xFFFFFFFF:
+                        # the device declined a member: the count is void, the window ends where the run began and
+                        # the file is the host reader's from its first byte (its exception is the error)
+                        m0, pos0, skip, status = chunk
+                        reason = _status_words(status.cpu().numpy(), m0 + ((fetched[4] >> 32) & 0xFFFFFFFF))
+                        path = cur.path
+                        cur.close()
+                        cur = None
+                        cur = _HostFile(path, skip)
+                        self.declined[path] = reason
+                        fill, host_valid = pos0, was_valid
+                        continue
+                    if chunk is not None and cur.at >= cur.n:
+                        self.inflated_by[cur.path] = "device"  # its last member passed (a newline may still follow)
+                    if n == 0:
+                        if eof:
+                            break
+                        if n_bytes == cap or not progressed:
+                            # not one whole record in a full window, or no room for one more member: a larger
+                            # window, not a loop
+                            cap *= 2
+                            bigger = torch.empty(cap, dtype=torch.uint8).pin_memory()
+                            if host_valid:
+                                bigger[:n_bytes].copy_(host[:n_bytes])
+                            host = bigger
+                            grown = torch.empty(cap, dtype=torch.uint8, device=dev)
+                            grown[:n_bytes].copy_(text[:n_bytes])
+                            text = grown
+                        fill = n_bytes
+                        continue
+                    if host_valid:
+                        yield Window(text, n_bytes, n, work, view[:n_bytes])
+                    else:
+                        yield _DeviceWindow(text, n_bytes, n, work)
+                    torch.cuda.current_stream(dev).synchronize()  # the copy out of `host` is done before it is refilled
+                    fill = n_bytes - consumed
+                    if fill and host_valid:
+                        view[:fill] = view[consumed:n_bytes].copy()
+                        dev_valid = False  # (the next window copies all of `view`, as it always has)
+                    elif fill:
+                        text[:fill].copy_(text[consumed:n_bytes].clone())  # device to device
+                    else:
+                        host_valid = True  # no carry: the next window starts clean on either side
                     if eof:
                         break
-                    if n_bytes == cap:  # not one whole record in a full window: a larger window, not a loop
-                        cap *= 2
-                        bigger = torch.empty(cap, dtype=torch.uint8).pin_memory()
-                        bigger[:n_bytes].copy_(host[:n_bytes])
-                        host = bigger
-                        text = torch.empty(cap, dtype=torch.uint8, device=dev)
-                    fill = n_bytes
-                    continue
-                yield Window(text, n_bytes, n, work, view[:n_bytes])
-                torch.cuda.current_stream(dev).synchronize()  # the copy out of `host` is done before it is refilled
-                fill = n_bytes - consumed
-                if fill:
-                    view[:fill] = view[consumed:n_bytes].copy()
-                if eof:
-                    break
+            finally:
+                if cur is not None:
+                    cur.close()
 
 
 def extract_spans(window: Window, spans):
@@ -355,7 +689,11 @@ class _DeviceColumns:
     def _spans(self):
         raise NotImplementedError
 
-    def _extract_windows(self, device=None, window_bytes: int = 256 << 20, max_records: Optional[int] = None):
+    inflated_by: dict = {}  # after columns(): path -> "device" / "host", as TextWindows.inflated_by
+    declined: dict = {}
+
+    def _extract_windows(self, device=None, window_bytes: int = 256 << 20, max_records: Optional[int] = None,
+                         inflate: str = DEFAULT_INFLATE):
         """Yields ``(first record index, n, [(seq tensor, qual tensor) per span])`` per window.  With
         ``max_records`` the stream ends after that many records and a bad record from there on is
         never seen, as an iterator that is not advanced past its consumer's last record never sees it."""
@@ -368,7 +706,9 @@ class _DeviceColumns:
             if not (0 <= start < end):
                 raise ValueError("barcode [%d, %d) is empty or negative" % (start, end))
         base = 0
-        for window in TextWindows(self._files, device, window_bytes):
+        windows = TextWindows(self._files, device, window_bytes, inflate=inflate)
+        self.inflated_by, self.declined = windows.inflated_by, windows.declined
+        for window in windows:
             columns, first_flagged, flags = extract_spans(window, spans)
             n = window.n_records
             if max_records is not None and base + n >= max_records:
@@ -423,11 +763,15 @@ class EmbeddedBarcodeGenerator(Reader, _DeviceColumns):
     def _spans(self):
         return list(self.embedded_barcodes)
 
-    def columns(self, device=None, window_bytes: int = 256 << 20, max_records: Optional[int] = None):
+    def columns(self, device=None, window_bytes: int = 256 << 20, max_records: Optional[int] = None,
+                inflate: str = DEFAULT_INFLATE):
         """Per window of at most ``window_bytes`` of decompressed text, a dict ``tag -> uint8 [n, L]``
         tensor on the device, in the order the host iterator lists the tags.  ``max_records`` ends the
-        stream after that many records; what follows them is neither extracted nor checked."""
-        for _, _, cols in self._extract_windows(device, window_bytes, max_records):
+        stream after that many records; what follows them is neither extracted nor checked.  ``inflate``
+        is ``TextWindows``'s: ``"auto"`` inflates BGZF files on the device, ``"host"`` none; ``inflated_by``
+        then says per file which it was."""
+        check_inflate(inflate)
+        for _, _, cols in self._extract_windows(device, window_bytes, max_records, inflate):
             out = {}
             for b, (seq, qual) in zip(self._spans(), cols):
                 out[b.sequence_tag] = seq
@@ -487,15 +831,17 @@ class BarcodeGeneratorWithCorrectedCellBarcodes(Reader, _DeviceColumns):
         cb = self.embedded_cell_barcode
         return cb.end - cb.start == self._error_mapping.barcode_length and self._header_comment_char is None
 
-    def columns(self, device=None, window_bytes: int = 256 << 20, max_records: Optional[int] = None):
+    def columns(self, device=None, window_bytes: int = 256 << 20, max_records: Optional[int] = None,
+                inflate: str = DEFAULT_INFLATE):
         """As :meth:`EmbeddedBarcodeGenerator.columns`, with ``CB`` after the cell barcode's two tags: the
         corrected bytes (the raw bytes where there is no correction) and, under ``"CB_index"``, the
         int32 whitelist file index, -1 where the record gets no ``CB``."""
         if not self.supports_columns:
             raise ValueError("the cell barcode's length differs from the whitelist's, or there is a "
                              "header_comment_char: iterate on the host")
+        check_inflate(inflate)
         key = consts.CELL_BARCODE_TAG_KEY
-        for _, _, cols in self._extract_windows(device, window_bytes, max_records):
+        for _, _, cols in self._extract_windows(device, window_bytes, max_records, inflate):
             out = {}
             for k, (b, (seq, qual)) in enumerate(zip(self._spans(), cols)):
                 out[b.sequence_tag] = seq

@@ -262,10 +262,17 @@ class FastqMetrics:
         e.g. ``16C10M``: ``C`` segments together are the cell barcode, ``M`` segments the UMI
     whitelist : str, optional
         accepted and unused, as in the reference
+    inflate : {"auto", "host"}
+        ``"auto"`` inflates BGZF-compressed files on the GPU (``fastq.TextWindows``), ``"host"`` none; after
+        ``compute()``, ``inflated_by`` maps each file to ``"device"`` or ``"host"`` and ``declined`` a file the
+        device gave back to the reason
     """
 
-    def __init__(self, r1_files: Union[str, Iterable[str]], read_structure: str, whitelist: Optional[str] = None):
+    def __init__(self, r1_files: Union[str, Iterable[str]], read_structure: str, whitelist: Optional[str] = None,
+                 inflate: str = fastq.DEFAULT_INFLATE):
         self.r1_files = [r1_files] if isinstance(r1_files, str) else list(r1_files)
+        self.inflate = fastq.check_inflate(inflate)
+        self.inflated_by, self.declined = {}, {}
         self.read_structure = read_structure
         self.whitelist = whitelist
         self.barcode_spans = kind_spans(read_structure, "C")
@@ -290,7 +297,8 @@ class FastqMetrics:
         slots = MIN_SLOTS
         while slots < int(initial_slots):
             slots *= 2
-        windows = fastq.TextWindows(self.r1_files, device, window_bytes)
+        windows = fastq.TextWindows(self.r1_files, device, window_bytes, inflate=self.inflate)
+        self.inflated_by, self.declined = windows.inflated_by, windows.declined
         dev = windows.device
         n_records = 0
         with torch.cuda.device(dev):

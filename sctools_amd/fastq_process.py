@@ -345,11 +345,11 @@ def _flag_error(path: str, record: int, flag: int) -> ValueError:
     return ValueError("%s: FASTQ record %d: %s" % (path, record, words))
 
 
-def _line_windows(path: str, device, window_bytes: int, keep_text: bool):
-    """Per window of ``path``: ``(n, (window, text, off, len))`` after ``sct_fqp_lines``; a flagged record raises.
-    With ``keep_text`` the text is a copy that outlives the window."""
-    base = 0
-    for window in fastq.TextWindows([path], device, window_bytes):
+def _line_windows(windows, keep_text: bool):
+    """Per window of the one file of the ``TextWindows`` ``windows``: ``(n, (window, text, off, len))`` after
+    ``sct_fqp_lines``; a flagged record raises.  With ``keep_text`` the text is a copy that outlives the window."""
+    base, path = 0, windows.files[0]
+    for window in windows:
         off, length, first_flagged, flags = window_lines(window)
         if first_flagged >= 0:
             raise _flag_error(path, base + first_flagged, int(flags[first_flagged].cpu()))
@@ -358,10 +358,10 @@ def _line_windows(path: str, device, window_bytes: int, keep_text: bool):
         base += window.n_records
 
 
-def _column_windows(path: str, spans, device, window_bytes: int):
-    """Per window of the R1 file ``path``: ``(n, [(seq, qual) per span])``; a short line raises."""
+def _column_windows(windows, spans):
+    """Per window of the R1 file of ``windows``: ``(n, [(seq, qual) per span])``; a short line raises."""
     base, max_end = 0, max(end for _, end in spans)
-    for window in fastq.TextWindows([path], device, window_bytes):
+    for window in windows:
         columns, first_flagged, flags = fastq.extract_spans(window, spans)
         if first_flagged >= 0:
             raise fastq.flag_error(window, base, first_flagged, flags, max_end)
@@ -395,12 +395,19 @@ class FastqProcess:
         GiB of input per shard where ``num_shards`` is not given
     num_shards : int, optional
     output_dir : str
+    inflate : {"auto", "host"}
+        ``"auto"`` inflates BGZF-compressed inputs on the GPU (``fastq.TextWindows``), ``"host"`` none; after
+        ``run()``, ``inflated_by`` maps every input file to ``"device"`` or ``"host"`` and ``declined`` a file the
+        device gave back to the reason
     """
 
     def __init__(self, r1_files, r2_files, i1_files=None, whitelist: Optional[str] = None,
                  barcode_length: Optional[int] = None, umi_length: Optional[int] = None,
                  read_structure: Optional[str] = None, sample_id: str = "", output_format: str = "BAM",
-                 bam_size: float = 1.0, num_shards: Optional[int] = None, output_dir: str = "."):
+                 bam_size: float = 1.0, num_shards: Optional[int] = None, output_dir: str = ".",
+                 inflate: str = fastq.DEFAULT_INFLATE):
+        self.inflate = fastq.check_inflate(inflate)
+        self.inflated_by, self.declined = {}, {}
         as_list = (lambda f: [f] if isinstance(f, (str, os.PathLike)) else list(f))
         self.r1_files, self.r2_files = as_list(r1_files), as_list(r2_files)
         self.i1_files = as_list(i1_files) if i1_files else []
@@ -470,19 +477,29 @@ class FastqProcess:
 
     def _batches(self, r1: str, r2: str, i1: Optional[str], corrector, fmt: int, dev, window_bytes: int):
         """Per R2 window of one triple: ``(Batch, (n_correct, n_corrected, n_uncorrectable))``."""
+        streams = [fastq.TextWindows([f], dev, window_bytes, inflate=self.inflate) if f else None for f in (r1, i1, r2)]
+        try:
+            yield from self._triple(streams, r1, r2, i1, corrector, fmt)
+        finally:  # who inflated the three files, as far as they were read
+            for stream in streams:
+                if stream is not None:
+                    self.inflated_by.update(stream.inflated_by)
+                    self.declined.update(stream.declined)
+
+    def _triple(self, streams, r1: str, r2: str, i1: Optional[str], corrector, fmt: int):
         import torch
 
         spans = self.cell_spans + self.umi_spans
         n_cell = len(self.cell_spans)
-        columns = _Taker(_column_windows(r1, spans, dev, window_bytes))
-        index_lines = _Taker(_line_windows(i1, dev, window_bytes, keep_text=True)) if i1 else None
+        columns = _Taker(_column_windows(streams[0], spans))
+        index_lines = _Taker(_line_windows(streams[1], keep_text=True)) if i1 else None
         done = 0
 
         def short(path, have):
             return ValueError("%s holds %d records, %s holds more: the files of a triple must hold the same number"
                               % (path, have, r2))
 
-        for n, (window, text, off, length) in _line_windows(r2, dev, window_bytes, keep_text=False):
+        for n, (window, text, off, length) in _line_windows(streams[2], keep_text=False):
             pieces = columns.take(n)
             if sum(b - a for _, a, b in pieces) < n:
                 raise short(r1, done + sum(b - a for _, a, b in pieces))

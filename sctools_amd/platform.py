@@ -30,6 +30,10 @@ From the reference's fastqpreprocessing tools: ``FastqMetrics --R1 FASTQ [--R1 F
 [--num-shards N] [--output-dir DIR] [--device N]`` (``fastqprocess.cpp``, ``fastq_slideseq.cpp``;
 ``sctools_amd/fastq_process.py``); ``FastqSlideseq`` is the same command.
 
+The four FASTQ commands (``Attach10xBarcodes``, ``AttachBarcodes``, ``FastqMetrics``, ``FastqProcess`` /
+``FastqSlideseq``) take ``--inflate auto|host``: with ``auto`` (the default) a BGZF-compressed FASTQ is inflated
+on the GPU, with ``host`` by Python's gzip like every other file (``fastq.TextWindows``).
+
 ``TagSort --bam-input BAM --metric-type cell|gene --compute-metric --metric-output CSV --barcode-tag T
 --umi-tag T --gene-tag T (their order is the sort order) [--gtf-file GTF] [--mitochondrial-gene-names-filename FILE]
 [--temp-folder DIR] [--alignments-per-thread N] [--nthreads N] [--device N] [--decoder auto|host]`` (``tagsort.cpp``,
@@ -250,9 +254,12 @@ class GenericPlatform:
         parser.add_argument("--sample-id", required=True, help="prefix of the four output files")
         parser.add_argument("--white-list", default=None, help="accepted and unused, as in the reference")
         parser.add_argument("--device", default=None, help="GPU index or torch device (default: current GPU)")
+        parser.add_argument("--inflate", default=fastq.DEFAULT_INFLATE, choices=list(fastq.INFLATE_MODES),
+                            help="who inflates BGZF-compressed FASTQ: auto = the GPU (any other file is read on the "
+                                 "host), host = the host for every file")
         args = parser.parse_args(args) if args is not None else parser.parse_args()
-        result = fastq_metrics.FastqMetrics(args.R1, args.read_structure, whitelist=args.white_list).compute(
-            device=args.device)
+        result = fastq_metrics.FastqMetrics(args.R1, args.read_structure, whitelist=args.white_list,
+                                            inflate=args.inflate).compute(device=args.device)
         result.write(args.sample_id)
         return 0
 
@@ -279,12 +286,15 @@ class GenericPlatform:
         parser.add_argument("--num-shards", type=int, default=None, help="number of shards (default: from --bam-size)")
         parser.add_argument("--output-dir", default=".", help="where the shards go (default: the current directory)")
         parser.add_argument("--device", default=None, help="GPU index or torch device (default: current GPU)")
+        parser.add_argument("--inflate", default=fastq.DEFAULT_INFLATE, choices=list(fastq.INFLATE_MODES),
+                            help="who inflates BGZF-compressed FASTQ: auto = the GPU (any other file is read on the "
+                                 "host), host = the host for every file")
         args = parser.parse_args(args) if args is not None else parser.parse_args()
         result = fastq_process.FastqProcess(
             args.R1, args.R2, i1_files=args.I1, whitelist=args.white_list, barcode_length=args.barcode_length,
             umi_length=args.umi_length, read_structure=args.read_structure, sample_id=args.sample_id,
             output_format=args.output_format, bam_size=args.bam_size, num_shards=args.num_shards,
-            output_dir=args.output_dir).run(device=args.device)
+            output_dir=args.output_dir, inflate=args.inflate).run(device=args.device)
         print("Total barcodes:%d\n correct:%d\ncorrected:%d\nuncorrectible:%d\nuncorrected:%f"
               % (result.n_reads, result.n_correct, result.n_corrected, result.n_uncorrectable,
                  100.0 * result.n_uncorrectable / max(result.n_reads, 1)))
@@ -314,8 +324,9 @@ class TenXV2(GenericPlatform):
                                            sequence_tag=consts.RAW_SAMPLE_BARCODE_TAG_KEY)
 
     @classmethod
-    def _tag_bamfile(cls, input_bamfile_name: str, output_bamfile_name: str, tag_generators, device=None) -> None:
-        bam.Tagger(input_bamfile_name, device=device).tag(output_bamfile_name, tag_generators)
+    def _tag_bamfile(cls, input_bamfile_name: str, output_bamfile_name: str, tag_generators, device=None,
+                     inflate: str = fastq.DEFAULT_INFLATE) -> None:
+        bam.Tagger(input_bamfile_name, device=device, inflate=inflate).tag(output_bamfile_name, tag_generators)
 
     @classmethod
     def _make_tag_generators(cls, r1, i1=None, whitelist=None) -> list:
@@ -346,9 +357,12 @@ class TenXV2(GenericPlatform):
                             help="cell barcode whitelist, one barcode per line; with it, CB is set where the raw cell "
                                  "barcode is on the list or one substitution away from it")
         parser.add_argument("--device", default=None, help="GPU index or torch device (default: current GPU)")
+        parser.add_argument("--inflate", default=fastq.DEFAULT_INFLATE, choices=list(fastq.INFLATE_MODES),
+                            help="who inflates BGZF-compressed FASTQ: auto = the GPU (any other file is read on the "
+                                 "host), host = the host for every file")
         args = parser.parse_args(args) if args is not None else parser.parse_args()
         cls._tag_bamfile(args.u2, args.output_bamfile, cls._make_tag_generators(args.r1, args.i1, args.whitelist),
-                         device=args.device)
+                         device=args.device, inflate=args.inflate)
         return 0
 
 
@@ -396,8 +410,9 @@ class BarcodePlatform(GenericPlatform):
         return cls._validate_barcode_input(int(given_value), 1)
 
     @classmethod
-    def _tag_bamfile(cls, input_bamfile_name: str, output_bamfile_name: str, tag_generators, device=None) -> None:
-        bam.Tagger(input_bamfile_name, device=device).tag(output_bamfile_name, tag_generators)
+    def _tag_bamfile(cls, input_bamfile_name: str, output_bamfile_name: str, tag_generators, device=None,
+                     inflate: str = fastq.DEFAULT_INFLATE) -> None:
+        bam.Tagger(input_bamfile_name, device=device, inflate=inflate).tag(output_bamfile_name, tag_generators)
 
     @classmethod
     def _make_tag_generators(cls, r1, i1=None, whitelist=None) -> list:
@@ -438,6 +453,9 @@ class BarcodePlatform(GenericPlatform):
                                 type=cls._validate_barcode_length,
                                 help="number of bases of the %s barcode (at least 1)" % where)
         parser.add_argument("--device", default=None, help="GPU index or torch device (default: current GPU)")
+        parser.add_argument("--inflate", default=fastq.DEFAULT_INFLATE, choices=list(fastq.INFLATE_MODES),
+                            help="who inflates BGZF-compressed FASTQ: auto = the GPU (any other file is read on the "
+                                 "host), host = the host for every file")
         args = parser.parse_args(args) if args else parser.parse_args()
         cls._validate_barcode_args(args)
         tags = {"cell": (consts.QUALITY_CELL_BARCODE_TAG_KEY, consts.RAW_CELL_BARCODE_TAG_KEY),
@@ -449,7 +467,7 @@ class BarcodePlatform(GenericPlatform):
                 setattr(cls, name + "_barcode", fastq.EmbeddedBarcode(start=start, end=start + length,
                                                                       quality_tag=quality_tag, sequence_tag=sequence_tag))
         cls._tag_bamfile(args.u2, args.output_bamfile, cls._make_tag_generators(args.r1, args.i1, args.whitelist),
-                         device=args.device)
+                         device=args.device, inflate=args.inflate)
         return 0
 
 

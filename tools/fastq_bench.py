@@ -145,6 +145,7 @@ class Phases:
     def __enter__(self):
         lib = fastq.load()
         self.wrap(fastq._ByteStream, "readinto", "read")
+        self.wrap(fastq._Inflater, "run", "stage_h2d_inflate_crc", sync=True)
         self.wrap(lib, "sct_fq_count", "h2d_kernels", sync=True)
         self.wrap(lib, "sct_fq_extract", "h2d_kernels", sync=True)
         self.wrap(barcode.ErrorsToCorrectBarcodesMap, "correct_barcodes", "correct", sync=True)
@@ -157,6 +158,52 @@ class Phases:
                 setattr(owner, name, inner)
             else:
                 delattr(owner, name)
+
+
+def write_fastq(path, block: bytes, reps: int, bgzf: bool, level: int = 4):
+    """``block`` ``reps`` times as a FASTQ file: Python gzip (one stream), or with ``bgzf`` members of 0xff00 bytes
+    and the EOF member, as bgzip and this project's shard writer lay them out."""
+    if not bgzf:
+        with gzip.open(path, "wb", compresslevel=level) as f:
+            for _ in range(reps):
+                f.write(block)
+        return
+    with open(path, "wb") as f:
+        buf = bytearray()
+
+        def flush(final=False):
+            while len(buf) >= 0xff00 or (final and buf):
+                chunk = bytes(buf[:0xff00])
+                del buf[:0xff00]
+                z = zlib.compressobj(level, zlib.DEFLATED, -15)
+                data = z.compress(chunk) + z.flush()
+                f.write(b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(data) + 25) + data
+                        + struct.pack("<II", zlib.crc32(chunk), len(chunk)))
+
+        for _ in range(reps):
+            buf += block
+            flush()
+        flush(final=True)
+        f.write(bytes([31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0]))
+
+
+def alternate(run, modes, runs):
+    """``run(mode)`` -> (seconds, phases): one warm-up of every mode, then ``runs`` of each in turn.  Per mode the
+    totals, their median and spread (max - min), and the phases of the median run."""
+    for mode in modes:
+        run(mode)
+    seen = {mode: [] for mode in modes}
+    for _ in range(runs):
+        for mode in modes:
+            seen[mode].append(run(mode))
+    out = {}
+    for mode, results in seen.items():
+        totals = sorted(t for t, _ in results)
+        median = totals[len(totals) // 2]
+        phases = next(ph for t, ph in results if t == median)
+        out[mode] = {"total_s": [round(t, 3) for t, _ in results], "median_s": round(median, 3),
+                     "spread_s": round(totals[-1] - totals[0], 3), "phases_of_median_s": phases}
+    return out
 
 
 def write_unaligned_bam(path, n, rng):
@@ -185,6 +232,46 @@ def write_unaligned_bam(path, n, rng):
                 flush()
         flush(final=True)
         f.write(bytes([31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0]))
+
+
+def bgzf_line(n_records, whitelist_file, runs, modes=("host", "auto")):
+    """Attach10xBarcodes on BGZF-compressed R1 / I1, ``inflate="host"`` and ``"auto"`` in turn in one process."""
+    rng = np.random.default_rng(5)
+    whitelist = [ln[:-1].encode() for ln in open(whitelist_file) if set(ln[:-1]) <= set("ACGT")]
+    with tempfile.TemporaryDirectory() as tmp:
+        r1, i1, u2 = os.path.join(tmp, "R1.fastq.gz"), os.path.join(tmp, "I1.fastq.gz"), os.path.join(tmp, "u2.bam")
+        block = r1_block(8192, rng, whitelist)
+        reps = max(1, n_records // len(block))
+        n = reps * len(block)
+        write_fastq(r1, b"".join(block), reps, bgzf=True)
+        write_fastq(i1, b"".join(rec.split(b"\n")[0] + b"\nACGTACGT\n+\nFFFFFFFF\n" for rec in block), reps, bgzf=True)
+        write_unaligned_bam(u2, n, rng)
+        sizes = {"r1_gz_bytes": os.path.getsize(r1), "i1_gz_bytes": os.path.getsize(i1), "u2_bam_bytes": os.path.getsize(u2),
+                 "r1_text_bytes": reps * len(b"".join(block))}
+        who = {}
+
+        def run(mode):
+            dst = os.path.join(tmp, "tagged_%s.bam" % mode)
+            generators = platform.TenXV2._make_tag_generators(r1, i1, whitelist_file)
+            tagger = bam.Tagger(u2, inflate=mode)
+            torch.cuda.synchronize()
+            with Phases() as phases:
+                t0 = time.perf_counter()
+                tagger.tag(dst, generators)
+                total = time.perf_counter() - t0
+            who[mode] = sorted(set(generators[0].inflated_by.values()) | set(generators[1].inflated_by.values()))
+            assert not generators[0].declined and not generators[1].declined
+            return total, {k: round(v, 3) for k, v in phases.seconds.items()}
+
+        out = alternate(run, modes, runs)
+        files = [open(os.path.join(tmp, "tagged_%s.bam" % mode), "rb").read() for mode in modes]
+        assert all(f == files[0] for f in files)
+        return {"what": "Attach10xBarcodes --whitelist end to end on BGZF FASTQ, --inflate host and auto in turn",
+                "records": n, "runs": runs, **sizes, "inflated_by": who, **out,
+                "phase_key": {"read": "host gunzip into the pinned window (inflate=host)",
+                              "stage_h2d_inflate_crc": "mapped file -> pinned buffer -> GPU, k_inflate, k_fq_crc32; synchronized",
+                              "h2d_kernels": "copy to the GPU (host path) + sct_fq_count + sct_fq_extract, synchronized",
+                              "correct": "sct_bc_correct", "write": "native BAM writer: record rebuild + BGZF deflate"}}
 
 
 def e2e_line(n_records, whitelist_file):
@@ -242,13 +329,21 @@ def main():
     ap.add_argument("--whitelist", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                                         "tests", "golden", "barcode", "1k-august-2016.txt"))
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    ap.add_argument("--bgzf", action="store_true", help="instead: Attach10xBarcodes on BGZF-compressed copies of the "
+                    "FASTQ inputs, the --inflate modes in turn (DESIGN.md section 19)")
+    ap.add_argument("--inflate", default="both", choices=["both", "auto", "host"], help="with --bgzf: the mode(s) to run")
+    ap.add_argument("--runs", type=int, default=5, help="with --bgzf: timed runs per mode, after one warm-up of each")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise RuntimeError("fastq_bench needs a ROCm GPU; a CPU run gives no timing")
     torch.cuda.set_device(0)
-    lines = [kernel_line(args.records, args.calls)]
-    if args.e2e_records > 0:
-        lines.append(e2e_line(args.e2e_records, args.whitelist))
+    if args.bgzf:
+        modes = ("host", "auto") if args.inflate == "both" else (args.inflate,)
+        lines = [bgzf_line(args.e2e_records, args.whitelist, args.runs, modes)]
+    else:
+        lines = [kernel_line(args.records, args.calls)]
+        if args.e2e_records > 0:
+            lines.append(e2e_line(args.e2e_records, args.whitelist))
     for line in lines:
         text = json.dumps(line, sort_keys=True)
         print(text, flush=True)

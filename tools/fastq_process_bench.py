@@ -171,6 +171,7 @@ class Phases(fastq_bench.Phases):
     def __enter__(self):
         lib = fastq.load()
         self.wrap(fastq._ByteStream, "readinto", "read")
+        self.wrap(fastq._Inflater, "run", "stage_h2d_inflate_crc", sync=True)
         for name in ("sct_fq_count", "sct_fq_extract", "sct_fqp_lines", "sct_fqp_shard", "sct_fqp_plan", "sct_fqp_emit_bam",
                      "sct_fqp_emit_fastq"):
             self.wrap(lib, name, "h2d_kernels", sync=True)
@@ -219,6 +220,48 @@ def e2e_line(n_records, n_shards, whitelist_file):
                               "other_s": "Python glue, allocation, the small reads of counts and sizes"}}
 
 
+def bgzf_line(n_records, n_shards, whitelist_file, runs, modes=("host", "auto")):
+    """FastqProcess on BGZF-compressed copies of the triple, ``inflate="host"`` and ``"auto"`` in turn in one process."""
+    rng = np.random.default_rng(5)
+    whitelist = [ln[:-1].encode() for ln in open(whitelist_file) if set(ln[:-1]) <= set("ACGT")]
+    with tempfile.TemporaryDirectory() as tmp:
+        blocks = triple_blocks(8192, rng, whitelist)
+        reps = max(1, n_records // 8192)
+        n = reps * 8192
+        paths, sizes = [], {}
+        for kind, block in zip(("R1", "R2", "I1"), blocks):
+            paths.append(os.path.join(tmp, kind + ".fastq.gz"))
+            fastq_bench.write_fastq(paths[-1], b"".join(block), reps, bgzf=True)
+            sizes[kind.lower() + "_gz_bytes"] = os.path.getsize(paths[-1])
+            sizes[kind.lower() + "_text_bytes"] = reps * len(b"".join(block))
+        who, counts = {}, {}
+
+        def run(mode):
+            out = os.path.join(tmp, "out_" + mode)
+            os.makedirs(out, exist_ok=True)
+            job = fp.FastqProcess([paths[0]], [paths[1]], [paths[2]], whitelist=whitelist_file, barcode_length=16,
+                                  umi_length=10, sample_id="bench", num_shards=n_shards, output_dir=out, inflate=mode)
+            torch.cuda.synchronize()
+            with Phases() as phases:
+                t0 = time.perf_counter()
+                result = job.run()
+                total = time.perf_counter() - t0
+            assert result.n_reads == n and not job.declined
+            who[mode] = sorted(set(job.inflated_by.values()))
+            counts[mode] = [result.n_correct, result.n_corrected, result.n_uncorrectable, result.shard_counts]
+            return total, {k: round(v, 3) for k, v in phases.seconds.items()}
+
+        out = fastq_bench.alternate(run, modes, runs)
+        assert all(counts[m] == counts[modes[0]] for m in modes)
+        return {"what": "FastqProcess --white-list end to end on BGZF FASTQ, BAM shards, --inflate host and auto in turn",
+                "records": n, "shards": n_shards, "runs": runs, **sizes, "inflated_by": who, **out,
+                "phase_key": {"read": "host gunzip into the pinned windows (inflate=host)",
+                              "stage_h2d_inflate_crc": "mapped file -> pinned buffer -> GPU, k_inflate, k_fq_crc32; synchronized",
+                              "h2d_kernels": "copy to the GPU (host path) + count, extract, lines, shard, plan, emit; synchronized",
+                              "correct": "sct_bc_correct", "d2h": "the emitted records to the host",
+                              "deflate": "native shard writer: BGZF deflate and file writes"}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--records", type=int, default=2_000_000)
@@ -228,12 +271,20 @@ def main():
     ap.add_argument("--whitelist", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                                         "tests", "golden", "barcode", "1k-august-2016.txt"))
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    ap.add_argument("--bgzf", action="store_true", help="instead: FastqProcess on BGZF-compressed copies of the triple, "
+                    "the --inflate modes in turn (DESIGN.md section 19)")
+    ap.add_argument("--inflate", default="both", choices=["both", "auto", "host"], help="with --bgzf: the mode(s) to run")
+    ap.add_argument("--runs", type=int, default=5, help="with --bgzf: timed runs per mode, after one warm-up of each")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise RuntimeError("fastq_process_bench needs a ROCm GPU; a CPU run gives no timing")
     torch.cuda.set_device(0)
-    lines = kernel_lines(args.records, args.calls, args.shards, args.whitelist)
-    if args.e2e_records > 0:
+    if args.bgzf:
+        modes = ("host", "auto") if args.inflate == "both" else (args.inflate,)
+        lines = [bgzf_line(args.e2e_records, args.shards, args.whitelist, args.runs, modes)]
+    else:
+        lines = kernel_lines(args.records, args.calls, args.shards, args.whitelist)
+    if args.e2e_records > 0 and not args.bgzf:
         lines.append(e2e_line(args.e2e_records, args.shards, args.whitelist))
         lines.append(fastq_bench.e2e_line(args.e2e_records, args.whitelist))
     for entry in lines:
