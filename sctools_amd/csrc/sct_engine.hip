@@ -265,7 +265,10 @@ struct SideStream {
   int dev = -1;
   hipStream_t s = nullptr, s_pair = nullptr;
   std::vector<hipEvent_t> evs;
-  bool synced = true;  // the caller's stream waits for everything queued here so far
+  hipEvent_t pair_ev = nullptr;  // the end of the work queued on s_pair (pair_mark)
+  bool synced = true;       // the caller's stream waits for everything queued here so far
+  bool pair_synced = true;  // the same for s_pair
+  bool alone = true;        // no other call on this device held a pair when this one was taken
   bool is_open() const { return s != nullptr; }
   hipError_t open(hipStream_t caller) {
     if (s) return from_caller(caller);
@@ -274,7 +277,6 @@ struct SideStream {
     if (e == hipSuccess) e = hipGetDevice(&prev);
     if (e != hipSuccess) return e;
     if (prev != dev && (e = hipSetDevice(dev)) != hipSuccess) return e;
-    bool alone = true;
     e = side_streams(dev, &s, &s_pair, &alone);
     if (e != hipSuccess) s = nullptr;
     if (prev != dev) (void)hipSetDevice(prev);
@@ -304,10 +306,36 @@ struct SideStream {
     if (e == hipSuccess) synced = true;
     return e;
   }
+  // The pool's second stream (round 8: the exact stream lanes): pair_fork() makes it wait for the
+  // work queued on the caller's stream so far and hands it out for launches, pair_mark() ends them,
+  // pair_join() makes the caller's stream wait for that end.
+  hipError_t pair_fork(hipStream_t caller, hipStream_t* out) {
+    hipEvent_t ev = nullptr;
+    hipError_t e = event(&ev);
+    if (e == hipSuccess) e = hipEventRecord(ev, caller);
+    if (e == hipSuccess) e = hipStreamWaitEvent(s_pair, ev, 0);
+    pair_synced = false;
+    *out = s_pair;
+    return e;
+  }
+  hipError_t pair_mark() {
+    hipError_t e = event(&pair_ev);
+    if (e == hipSuccess) e = hipEventRecord(pair_ev, s_pair);
+    if (e != hipSuccess) pair_ev = nullptr;
+    return e;
+  }
+  hipError_t pair_join(hipStream_t caller) {
+    if (pair_synced) return hipSuccess;
+    if (!pair_ev) return hipStreamSynchronize(s_pair);
+    hipError_t e = hipStreamWaitEvent(caller, pair_ev, 0);
+    if (e == hipSuccess) pair_synced = true;
+    return e;
+  }
   ~SideStream() {
     // an early return (an error, or the global-sort redo that reuses the workspace): nothing may
     // still write into the workspace once the call is left
     if (s && !synced) (void)hipStreamSynchronize(s);
+    if (s && !pair_synced) (void)hipStreamSynchronize(s_pair);
     for (hipEvent_t ev : evs) (void)hipEventDestroy(ev);
     if (s) side_streams_release(dev, s, s_pair);
   }
@@ -758,6 +786,35 @@ int pipeline(const sct_plan_t* plan, const sct_records_t* rec, const uint8_t* ge
   if (planned) level1_fills(L, ws, n, n_ent, l1, fb, may_plan);
   rc = launch_fills(fb, s);
   if (rc) return rc;
+  // Round 8: on the planned bucket path with exact floats the quality-stream lanes run as a kernel
+  // of their own (segment.h k_stream_lanes) on the side pool's second stream, and the key pass
+  // without them.  They fork here (the fills above zeroed the partial rows and gwide): beside the
+  // level-1 plan and its classification, which are latency-bound, and whatever is left beside the
+  // key pass.  (A fork after the key pass, beside the partition levels >= 2, measured no gain: the
+  // early big buckets fill that stretch)  SCT_STREAM_LANES=fused (a test
+  // switch; pre: this path, the default) keeps the one launch, and so does a call that finds another
+  // call's pair in use on the device (the pool would then open further streams, and a process has 4
+  // hardware queues).
+  SideStream side;
+  const char* no_side = getenv("SCT_NO_SIDE");
+  const bool use_side = bucket && planned && exact && !(no_side && no_side[0] == '1');
+  const char* lanes_sw = getenv("SCT_STREAM_LANES");
+  bool split = use_side && streams && n > 0 && !(lanes_sw && !strcmp(lanes_sw, "fused"));
+  if (split) {
+    HIPCHK(side.open(s));
+    split = side.alone;
+  }
+  if (split) {
+    hipStream_t sp = nullptr;
+    HIPCHK(side.pair_fork(s, &sp));
+    uint32_t* gw = gene ? gwide : nullptr;
+    if (cell) {
+      LAUNCH_N("stream_lanes", n, k_stream_lanes<true>, tgrid, dim3(kBlock), sp, rc2, n, toff, hbits, partials, gw);
+    } else {
+      LAUNCH_N("stream_lanes", n, k_stream_lanes<false>, tgrid, dim3(kBlock), sp, rc2, n, toff, hbits, partials, gw);
+    }
+    HIPCHK(side.pair_mark());
+  }
   if (planned) {
     rc = bucket_level1_plan(L, ws, kc, n, n_ent, b, ent_start, l1, s);
     if (rc) return rc;
@@ -777,10 +834,11 @@ int pipeline(const sct_plan_t* plan, const sct_records_t* rec, const uint8_t* ge
 
   if (bucket) {
     uint64_t* pay = at<uint64_t>(ws, L.pay_a);  // (the bucket path writes Pay records through `keys`)
-    rc = streams ? launch_build_keys<true, true>(cell, gene, tgrid, s, kc, rc2, mito, n, toff, b, pay, nullptr, hbits,
-                                                 ent_start, partials, gcounts, L.n_buckets, &ctl->err, gwide, gtoff, l1)
-                 : launch_build_keys<true, false>(cell, gene, tgrid, s, kc, rc2, mito, n, toff, b, pay, nullptr, hbits,
-                                                  ent_start, partials, gcounts, L.n_buckets, &ctl->err, gwide, gtoff, l1);
+    rc = streams && !split
+             ? launch_build_keys<true, true>(cell, gene, tgrid, s, kc, rc2, mito, n, toff, b, pay, nullptr, hbits,
+                                             ent_start, partials, gcounts, L.n_buckets, &ctl->err, gwide, gtoff, l1)
+             : launch_build_keys<true, false>(cell, gene, tgrid, s, kc, rc2, mito, n, toff, b, pay, nullptr, hbits,
+                                              ent_start, partials, gcounts, L.n_buckets, &ctl->err, gwide, gtoff, l1);
   } else {
     rc = streams ? launch_build_keys<false, true>(cell, gene, tgrid, s, kc, rc2, mito, n, toff, b, B.ka, B.va, hbits,
                                                   ent_start, partials, gcounts, L.n_buckets, &ctl->err, gwide, gtoff,
@@ -802,10 +860,7 @@ int pipeline(const sct_plan_t* plan, const sct_records_t* rec, const uint8_t* ge
   // Round 6: a side stream forked after the key pass (planned bucket path, exact floats) runs the
   // gene view's plan and the big buckets of levels 0-1 beside the partition levels >= 2 and the
   // hash tiles, and the cell rows' finalize beside the gene view
-  SideStream side;
   hipEvent_t plan_done = nullptr;
-  const char* no_side = getenv("SCT_NO_SIDE");
-  const bool use_side = bucket && planned && exact && !(no_side && no_side[0] == '1');
   uint32_t* gcur = gene ? at<uint32_t>(ws, L.gcursor) : nullptr;
   int64_t* gwork = gene ? at<int64_t>(ws, L.gwork) : nullptr;
   int64_t* n_gwork = at<int64_t>(ws, L.scalars) + 4;
@@ -827,6 +882,7 @@ int pipeline(const sct_plan_t* plan, const sct_records_t* rec, const uint8_t* ge
       if (wf.s2) HIPCHK(hipStreamSynchronize(wf.s2));  // (its workspace is reused by the redo)
       if (wf.s3) HIPCHK(hipStreamSynchronize(wf.s3));
       if (side.is_open()) HIPCHK(hipStreamSynchronize(side.s));
+      if (side.is_open() && !side.pair_synced) HIPCHK(hipStreamSynchronize(side.s_pair));  // (the stream lanes)
       return pipeline(plan, rec, gene_is_mito, ws, ws_bytes, out_i, out_f, capacity, n_rows, gene_partials, s,
                       false);
     }
@@ -850,6 +906,10 @@ int pipeline(const sct_plan_t* plan, const sct_records_t* rec, const uint8_t* ge
     }
   }
 
+  // the stream lanes (k_stream_lanes on the pair stream) are complete before the rows' finalize reads
+  // their slots, on whichever stream it runs (the side stream forks from the caller's below), and
+  // before k_gene_emit reads gwide
+  if (split) HIPCHK(side.pair_join(s));
   if (out_i) {
     const char* no_sfin = getenv("SCT_NO_SIDE_FIN");
     const bool side_fin = side.is_open() && gene && !(no_sfin && no_sfin[0] == '1');

@@ -802,4 +802,31 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))
                                                  kGene ? gwide : nullptr);
 }
 
+// The kStreams part of k_build_keys_run as a launch of its own (round 8): one block per key-pass
+// tile, the same run ids off the head bitmap and the scanned tile counts, the same stream_tile, so
+// the rows are bit-identical (the lanes are integer sums added with atomics: order-free).  It shares
+// nothing with the key pass but those run ids, so the host runs it on a side stream beside the
+// latency-bound kernels around the key pass (sct_engine.hip pipeline), and the key pass runs without
+// the lanes (kStreams = false).  gwide: nullptr unless the gene view follows (k_gene_emit reads it).
+template <bool kCell>
+__global__ void __launch_bounds__(kBlock) k_stream_lanes(RecCols r, int64_t n, const uint64_t* __restrict__ tile_off,
+                                                         const uint64_t* __restrict__ head_bits,
+                                                         int64_t* __restrict__ partials,
+                                                         uint32_t* __restrict__ gwide) {
+  __shared__ uint64_t s_scan[kWaves + 1];
+  __shared__ uint64_t s_hb[kKTile / 64];
+  __shared__ uint16_t s_wpre[kKTile / 64];
+  __shared__ StreamTabs s_tab[1];
+  __shared__ double s_rcp[kRcpN];
+  const int64_t base = (int64_t)blockIdx.x * kKTile;
+  if (base >= n) return;  // (block-uniform; the grid is cdiv(n, kKTile))
+  const int tile_n = (int)((n - base) < kKTile ? (n - base) : kKTile);
+  fill_rcp(s_rcp);  // visible after tile_run_ids' barriers
+  fill_stream_tabs<kCell>(r, base, s_tab);
+  uint32_t my_heads, my_ex, n_heads;
+  const int64_t ebase = tile_run_ids(head_bits, base, n, tile_off[(size_t)blockIdx.x * kKTilesPerBlock], s_hb, s_scan,
+                                     &my_heads, &my_ex, &n_heads, s_wpre);
+  stream_tile<kCell>(r, base, tile_n, my_heads, my_ex, ebase, s_rcp, s_tab, partials, gwide);
+}
+
 }  // namespace sct
