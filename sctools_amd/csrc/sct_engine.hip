@@ -39,6 +39,7 @@
 #include "radix.h"
 #include "reduce.h"
 #include "segment.h"
+#include "streams.h"
 #include "tagsort.h"
 #include "tsmetrics.h"
 #include "util.h"
@@ -163,447 +164,313 @@ int check_plan(const sct_plan_t* plan, const sct_records_t* rec) {
   return SCT_OK;
 }
 
+// ---------------- the metric step ----------------
+// Its switches (tests and experiments; DESIGN.md §16 lists what each turns off and the test that
+// uses it), read once per call: the tests flip them between calls of one process.
+bool env_is(const char* name, char v) {
+  const char* x = getenv(name);
+  return x && x[0] == v;
+}
+int env_int_in(const char* name, int lo, int hi) {  // 0 when unset or outside [lo, hi]
+  const int v = getenv(name) ? atoi(getenv(name)) : 0;
+  return v >= lo && v <= hi ? v : 0;
+}
+struct StepSwitches {  // (constructing one reads the environment)
+  bool no_early_big = env_is("SCT_NO_EARLY_BIG", '1');
+  bool no_level_big = env_is("SCT_NO_LEVEL_BIG", '1');
+  bool big_beside_hash = env_is("SCT_BIG_BESIDE_HASH", '1');
+  bool no_wf_gate = env_is("SCT_NO_WF_GATE", '1');
+  bool no_l1_plan = env_is("SCT_NO_L1_PLAN", '1');
+  bool force_global_sort = env_is("SCT_FORCE_GLOBAL_SORT", '1');
+  bool no_prefill = env_is("SCT_NO_PREFILL", '1');
+  bool no_side = env_is("SCT_NO_SIDE", '1');
+  bool no_side_fin = env_is("SCT_NO_SIDE_FIN", '1');
+  bool lanes_fused = getenv("SCT_STREAM_LANES") && !strcmp(getenv("SCT_STREAM_LANES"), "fused");  // else "pre"
+  // 1..8: every entity's first level on that many bits, not the width its size asks for (8: rounds < 7)
+  int l1_bits = env_int_in("SCT_L1_BITS", 1, kRadixBits);
+};
+
+// The views a kernel template is instantiated for: F(cell view, gene partials) over (true, true),
+// (true, false), (false, false) -- gene runs never emit gene partials -- and F(cell view).
+// Further arguments are passed on to F.
+#define SCT_VIEW3(cell, gene, F, ...)                       \
+  do {                                                      \
+    if ((cell) && (gene)) { F(true, true, ##__VA_ARGS__); } \
+    else if (cell) { F(true, false, ##__VA_ARGS__); }       \
+    else { F(false, false, ##__VA_ARGS__); }                \
+  } while (0)
+#define SCT_VIEW2(cell, F) \
+  do {                     \
+    if (cell) { F(true); } \
+    else { F(false); }     \
+  } while (0)
+
 // heads + scan of the entity column; with `dup_check`, also flags cell ids seen in two runs.
 // Copies (n_entities, dup flag) to the host and synchronizes.
 // pre: a fill queued behind the count's copy (round 6: it runs while the host waits for the count)
 // publish (the pipeline: the workspace is a whole one, not sct_count_entities' prefix; round 7): the
 // head bitmap and, queued behind the scan, the entity starts, also written while the host waits
-int count_runs(const int32_t* ent, int64_t n, void* ws, const Layout& L, bool dup_check, int32_t n_ids,
-               int64_t* n_ent, bool* dup, hipStream_t s, FillBatch* pre = nullptr, bool publish = false) {
+struct CountOpts {
+  bool dup_check = false, publish = false;
+  int32_t n_ids = 0;
+  FillBatch* pre = nullptr;
+};
+int count_runs(const int32_t* ent, int64_t n, void* ws, const Layout& L, const CountOpts& o, int64_t* n_ent,
+               bool* dup, hipStream_t s) {
   const int64_t tiles = cdiv(n, kTile);
   uint64_t* tc = at<uint64_t>(ws, L.tile_cnt);
   uint64_t* sc = at<uint64_t>(ws, L.scalars);
-  uint64_t* hb = publish ? at<uint64_t>(ws, L.head_bits) : nullptr;
-  uint32_t* seen = nullptr;
+  uint64_t* hb = o.publish ? at<uint64_t>(ws, L.head_bits) : nullptr;
+  uint32_t* seen = o.dup_check ? at<uint32_t>(ws, L.seen) : nullptr;
   FillBatch fb;
-  if (dup_check) {
-    seen = at<uint32_t>(ws, L.seen);
-    fb.add(seen, sizeof(uint32_t) * (size_t)n_ids);
-  }
+  if (seen) fb.add(seen, sizeof(uint32_t) * (size_t)o.n_ids);
   fb.add(sc, 2 * sizeof(uint64_t));
   if (int rc = launch_fills(fb, s)) return rc;
   if (((uintptr_t)ent & 15) == 0) {
-    LAUNCH_N("heads", n, k_heads4, dim3((unsigned)tiles), dim3(kBlock), s, ent, n, tc, seen, (uint32_t)n_ids, sc + 1, hb);
+    LAUNCH_N("heads", n, k_heads4, dim3((unsigned)tiles), dim3(kBlock), s, ent, n, tc, seen, (uint32_t)o.n_ids, sc + 1, hb);
   } else {
-    LAUNCH_N("heads", n, k_heads, dim3((unsigned)tiles), dim3(kBlock), s, ent, n, tc, seen, (uint32_t)n_ids, sc + 1, hb);
+    LAUNCH_N("heads", n, k_heads, dim3((unsigned)tiles), dim3(kBlock), s, ent, n, tc, seen, (uint32_t)o.n_ids, sc + 1, hb);
   }
   LAUNCH("scan", k_scan_wide, dim3(1), dim3(kScanWide), s, tc, tiles, sc);
-  if (publish) {
+  if (o.publish) {
     LAUNCH("ent_starts", k_ent_starts, dim3((unsigned)cdiv(tiles, kWaves)), dim3(kBlock), s, (const uint64_t*)hb,
            (const uint64_t*)tc, (const uint64_t*)sc, n, L.max_ent, at<int64_t>(ws, L.ent_start));
   }
   uint64_t host[2] = {0, 0};
-  if (pre) {
+  if (o.pre) {
     if (int rb = readback_start(sc, sizeof(host), s)) return rb;
-    if (int rc = launch_fills(*pre, s)) return rc;
+    if (int rc = launch_fills(*o.pre, s)) return rc;
     if (int rb = readback_finish(host, sizeof(host))) return rb;
   } else {
     if (int rb = readback(host, sc, sizeof(host), s)) return rb;
   }
   *n_ent = (int64_t)host[0];
   if (dup) *dup = host[1] & 1;
-  if (host[1] & 2) return fail(SCT_EINVAL, "an entity id lies outside [0, %d)", n_ids);
+  if (host[1] & 2) return fail(SCT_EINVAL, "an entity id lies outside [0, %d)", o.n_ids);
   return SCT_OK;
 }
 
-template <bool kWideK1>
-int launch_hash_tile(bool cell, bool gene, dim3 grid, hipStream_t s, const uint16_t* bdesc, const uint32_t* bent,
-                     const Pay* pa, const Pay* pb, int64_t n,
-                     const Bits& b, int64_t* partials, uint16_t* dflags) {
-  if (cell && gene) {
-    LAUNCH_N("hash_tile", n, (k_hash_tile<true, true, kWideK1>), grid, dim3(kHBlock), s, bdesc, bent, pa, pb, n,
-           b, partials, dflags);
-  } else if (cell) {
-    LAUNCH_N("hash_tile", n, (k_hash_tile<true, false, kWideK1>), grid, dim3(kHBlock), s, bdesc, bent, pa, pb, n,
-           b, partials, dflags);
+// Key bits (a pure host function).  Bucket path (default): [k1' | k2 | hash], KB <= kMaxKeyBits,
+// entities implied by the record ranges.  Global-sort path: [run | k1' | k2 | hash], padded to whole
+// radix digits.  *used: the bits before the hash.
+int plan_key_bits(bool bucket, int64_t n_ent, Bits* b, int* used) {  // (b->k1, b->k2 are set)
+  if (bucket) {
+    b->e = 0;
+    *used = b->k1 + b->k2;
+    b->h = kMaxKeyBits - *used < 8 ? kMaxKeyBits - *used : 8;
   } else {
-    LAUNCH_N("hash_tile", n, (k_hash_tile<false, false, kWideK1>), grid, dim3(kHBlock), s, bdesc, bent, pa, pb,
-           n, b, partials, dflags);
+    b->e = bitlen((uint64_t)n_ent);
+    *used = b->e + b->k1 + b->k2;
+    if (*used > 63) return fail(SCT_EINVAL, "packed key needs %d bits (> 63)", *used);
+    // fill the last radix digit with fragment-hash bits (same pass count), every shift < 64
+    const int padded = ((*used + kRadixBits - 1) / kRadixBits) * kRadixBits;
+    b->h = (padded > 63 ? 63 : padded) - *used;
+    if (b->h > 32) b->h = 32;
+  }
+  if (b->k1 > 0) {  // spread neighbouring k1 ids over the top key digits (odd multiplier, bijective)
+    b->mul = 0x9E3779B1u & b->k1_mask();
+    b->mul |= 1u;
+    uint32_t inv = b->mul;  // Newton: inverse mod 2^32, then mod 2^k1
+    for (int it = 0; it < 5; it++) inv *= 2u - b->mul * inv;
+    b->inv = inv & b->k1_mask();
   }
   return SCT_OK;
 }
 
-// The first partition level planned before the key pass (segment.h k_level1_plan): run ids and
-// per-entity digit counts, level 0, then level 1's classification with a grid sized for the most
-// segments there can be (the device count bounds it): l1.hist then holds every segment child's start.
-// No host wait.
-// (its buffers -- bdesc, the level-0 counters, l1.hist -- are zeroed by the caller: level1_fills)
-void level1_fills(const Layout& L, void* ws, int64_t n, int64_t n_ent, const L1Plan& l1, FillBatch& fb,
-                  bool bdesc_done) {
-  if (!bdesc_done) fb.add(at<uint16_t>(ws, L.bdesc), sizeof(uint16_t) * (size_t)n);
-  fb.add(level0_ctr(ws, L), 3 * sizeof(uint32_t));
-  fb.add(l1.hist, sizeof(uint32_t) * kRadix * (size_t)n_ent);
-}
-
-int bucket_level1_plan(const Layout& L, void* ws, const KeyCols& kc, int64_t n, int64_t n_ent, const Bits& b,
-                       const int64_t* ent_start, const L1Plan& l1, hipStream_t s) {
-  uint16_t* bdesc = at<uint16_t>(ws, L.bdesc);
-  uint32_t* bent = at<uint32_t>(ws, L.bent);
-  BucketCtl* ctl = bucket_ctl(ws, L);
-  uint32_t* ctr0 = level0_ctr(ws, L);
-  const int KB = b.k1 + b.k2 + b.h;
-  LAUNCH_N("level1_plan", n, k_level1_plan, dim3((unsigned)cdiv(n, kKTile)), dim3(kBlock), s,
-           (const uint64_t*)at<uint64_t>(ws, L.head_bits), kc.k1, kc.n_k1, n,
-           (const uint64_t*)at<uint64_t>(ws, L.tile_cnt), b, ent_start, l1);
-  LAUNCH("bucket_level0", k_bucket_level0, dim3((unsigned)cdiv(n_ent, kBlock)), dim3(kBlock), s, ent_start, n_ent, n,
-         bdesc, bent, at<Seg>(ws, L.seg_a), at<Work>(ws, L.work_a), at<Seg>(ws, L.bigs), ctl, ctr0);
-  const int64_t max_seg = n_ent < n / (kBigCap + 1) + 1 ? n_ent : n / (kBigCap + 1) + 1;
-  if (max_seg > L.max_seg) return fail(SCT_ENOMEM, "level 1: %lld segments exceed the workspace", (long long)max_seg);
-  LAUNCH("bucket_classify", k_bucket_classify, dim3((unsigned)max_seg), dim3(kBlock), s,
-         (const Seg*)at<Seg>(ws, L.seg_a), l1.hist, at<uint32_t>(ws, L.seg_cur), l1.bits, b.k1, b.k1 + b.k2, KB,
-         1, 1, bdesc, bent, at<Seg>(ws, L.seg_b), at<Work>(ws, L.work_b), at<Seg>(ws, L.giants), at<Seg>(ws, L.bigs),
-         ctl, (const uint32_t*)ctr0);
-  return SCT_OK;
-}
-
-// One stream of the device's side-stream pool (below) for work beside the caller's stream (round 6):
-// from_caller() makes it wait for the work queued on the caller's stream so far, to_caller() the
-// reverse; use() hands out the stream for a launch.
-hipError_t side_streams(int dev, hipStream_t* s2, hipStream_t* s3, bool* alone);
-void side_streams_release(int dev, hipStream_t s2, hipStream_t s3);
-struct SideStream {
-  int dev = -1;
-  hipStream_t s = nullptr, s_pair = nullptr;
-  std::vector<hipEvent_t> evs;
-  hipEvent_t pair_ev = nullptr;  // the end of the work queued on s_pair (pair_mark)
-  bool synced = true;       // the caller's stream waits for everything queued here so far
-  bool pair_synced = true;  // the same for s_pair
-  bool alone = true;        // no other call on this device held a pair when this one was taken
-  bool is_open() const { return s != nullptr; }
-  hipError_t open(hipStream_t caller) {
-    if (s) return from_caller(caller);
-    int prev = 0;
-    hipError_t e = hipStreamGetDevice(caller, &dev);
-    if (e == hipSuccess) e = hipGetDevice(&prev);
-    if (e != hipSuccess) return e;
-    if (prev != dev && (e = hipSetDevice(dev)) != hipSuccess) return e;
-    e = side_streams(dev, &s, &s_pair, &alone);
-    if (e != hipSuccess) s = nullptr;
-    if (prev != dev) (void)hipSetDevice(prev);
-    return e == hipSuccess ? from_caller(caller) : e;
-  }
-  hipStream_t use() {
-    synced = false;
-    return s;
-  }
-  hipError_t event(hipEvent_t* ev) {
-    hipError_t e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
-    if (e == hipSuccess) evs.push_back(*ev);
-    return e;
-  }
-  hipError_t from_caller(hipStream_t caller) {
-    hipEvent_t ev = nullptr;
-    hipError_t e = event(&ev);
-    if (e == hipSuccess) e = hipEventRecord(ev, caller);
-    if (e == hipSuccess) e = hipStreamWaitEvent(s, ev, 0);
-    return e;
-  }
-  hipError_t to_caller(hipStream_t caller) {
-    hipEvent_t ev = nullptr;
-    hipError_t e = event(&ev);
-    if (e == hipSuccess) e = hipEventRecord(ev, s);
-    if (e == hipSuccess) e = hipStreamWaitEvent(caller, ev, 0);
-    if (e == hipSuccess) synced = true;
-    return e;
-  }
-  // The pool's second stream (round 8: the exact stream lanes): pair_fork() makes it wait for the
-  // work queued on the caller's stream so far and hands it out for launches, pair_mark() ends them,
-  // pair_join() makes the caller's stream wait for that end.
-  hipError_t pair_fork(hipStream_t caller, hipStream_t* out) {
-    hipEvent_t ev = nullptr;
-    hipError_t e = event(&ev);
-    if (e == hipSuccess) e = hipEventRecord(ev, caller);
-    if (e == hipSuccess) e = hipStreamWaitEvent(s_pair, ev, 0);
-    pair_synced = false;
-    *out = s_pair;
-    return e;
-  }
-  hipError_t pair_mark() {
-    hipError_t e = event(&pair_ev);
-    if (e == hipSuccess) e = hipEventRecord(pair_ev, s_pair);
-    if (e != hipSuccess) pair_ev = nullptr;
-    return e;
-  }
-  hipError_t pair_join(hipStream_t caller) {
-    if (pair_synced) return hipSuccess;
-    if (!pair_ev) return hipStreamSynchronize(s_pair);
-    hipError_t e = hipStreamWaitEvent(caller, pair_ev, 0);
-    if (e == hipSuccess) pair_synced = true;
-    return e;
-  }
-  ~SideStream() {
-    // an early return (an error, or the global-sort redo that reuses the workspace): nothing may
-    // still write into the workspace once the call is left
-    if (s && !synced) (void)hipStreamSynchronize(s);
-    if (s && !pair_synced) (void)hipStreamSynchronize(s_pair);
-    for (hipEvent_t ev : evs) (void)hipEventDestroy(ev);
-    if (s) side_streams_release(dev, s, s_pair);
-  }
+// One call of the RUN-mode pipeline (entity = runs of the cell column, or of the gene column in gene
+// mode; GROUPED runs the cell view).  It writes partial rows into the workspace, output rows if
+// out_i / out_f are set, and grouped gene partials (cell view) if gene_partials is set.
+struct StepCall {
+  const sct_plan_t* plan;
+  const sct_records_t* rec;
+  const uint8_t* gene_is_mito;
+  void* ws;
+  size_t ws_bytes;
+  int64_t* out_i;
+  double* out_f;
+  int64_t capacity;
+  int64_t* n_rows;
+  int64_t* gene_partials;
+  hipStream_t s;
 };
 
-// bucket.h driver: level 0 classification, MSD levels until no segment exceeds kBCap, then
-// the hash-tile pass (+ giants).  One host wait per level to size the next level's launches,
-// for a copy queued right after the classification: the level's scatter runs meanwhile.
-// planned: level 0 and level 1 ran before the key pass (bucket_level1_plan), and the key pass wrote
-// the level-1 children: the loop starts at level 2.
-// Returns 1 (not an error code) when build_keys saw a mapped ref id the payload cannot hold:
-// the caller then reruns on the global-sort path.
-int bucket_distinct(const Layout& L, void* ws, int64_t n, int64_t n_ent, const int64_t* ent_start,
-                    const uint8_t* mito, const Bits& b, bool cell, bool gene, int64_t* partials, uint16_t* dflags,
-                    bool planned, hipStream_t s, SideStream& side) {
-  if (n == 0) return SCT_OK;
-  Pay* pa = at<Pay>(ws, L.pay_a);
-  Pay* pb = at<Pay>(ws, L.pay_b);
+// What the stages of one step share: the call, switches, streams, path flags and workspace pointers.
+struct Step {
+  const StepCall& c;
+  const StepSwitches& sw;
+  const Layout L;
+  StepStreams st{c.s};
+  void* const ws = c.ws;
+  const hipStream_t s = c.s;
+  const int64_t n = c.rec->n;
+  int64_t n_ent = 0;
+  const bool cell = c.plan->mode != SCT_MODE_GENE, gene = c.gene_partials != nullptr;
+  const bool exact = c.plan->float_mode == SCT_FLOAT_EXACT_SUM;
+  const bool streams = exact && c.out_i;  // exact mean / variance lanes of the output rows beside the keys
+  // bucket: the bucket path, not the global sort.  plannable: its first partition level can be planned
+  // before the key pass -- the digit comes from k1 alone (segment.h k_level1_plan), so the key pass
+  // writes the level-1 children itself; planned: and there are entities.
+  bool bucket, plannable, planned = false;
+  bool use_side = false;  // the side stream of the planned bucket path with exact floats (round 6)
+  bool split = false;     // the stream lanes in their own kernel on the pair's second stream (round 8)
+  Bits b;
+  int used = 0;
+  const KeyCols kc{cell ? c.rec->gene : c.rec->cell, c.rec->umi,
+                   (uint32_t)(cell ? c.plan->n_gene_ids : c.plan->n_cell_ids), (uint32_t)c.plan->n_umi_ids};
+  const RecCols rc{c.rec->ref,  c.rec->pos,     c.rec->gq_sum, c.rec->gq_len,  c.rec->gq_gt30, c.rec->bits,
+                   c.rec->xf,   c.rec->cy_gt30, c.rec->cy_len, c.rec->uy_gt30, c.rec->uy_len};
+  // the bucket path's payloads are the global-sort path's keys and values (layout_for)
+  const SortBuffers B{at<uint64_t>(ws, L.pay_a), at<uint64_t>(ws, L.pay_b), at<uint32_t>(ws, L.pay_a + L.half),
+                      at<uint32_t>(ws, L.pay_b + L.half), at<uint32_t>(ws, L.counts), at<uint32_t>(ws, L.offsets),
+                      at<uint64_t>(ws, L.scan_sums), L.count_cap};
+  L1Plan l1{};
+  const uint8_t* mito = c.gene_is_mito;
+  hipEvent_t plan_done = nullptr, lanes_done = nullptr;
+  // the workspace.  toff: the key-pass tiles' offsets (tile offsets are per kTile); hbits, ent_start:
+  // run heads (one bit per record) and entity starts (+ the sentinel ent_start[n_ent] = n): count_runs
+  const uint64_t *toff = at<uint64_t>(ws, L.tile_cnt), *hbits = at<uint64_t>(ws, L.head_bits);
+  const int64_t* ent_start = at<int64_t>(ws, L.ent_start);
+  int64_t* partials = at<int64_t>(ws, L.partials);
+  uint32_t *gcounts = gene ? at<uint32_t>(ws, L.gcounts) : nullptr, *gtoff = gene ? at<uint32_t>(ws, L.gtoff) : nullptr;
+  uint32_t* gcur = gene ? at<uint32_t>(ws, L.gcursor) : nullptr;
+  int64_t *gwork = gene ? at<int64_t>(ws, L.gwork) : nullptr, *n_gwork = at<int64_t>(ws, L.scalars) + 4;
+  uint16_t* dflags = gene ? at<uint16_t>(ws, L.dflags) : nullptr;
+  // gene payload format: narrow (8 B) unless an operand does not fit (checked by the exact-stream
+  // pass; without it the wide format is used)
+  uint32_t* gwide = reinterpret_cast<uint32_t*>(at<uint64_t>(ws, L.scalars) + 16);
+  BucketCtl* ctl = bucket_ctl(ws, L);
+  uint32_t* ctr0 = level0_ctr(ws, L);
+  Pay *pa = at<Pay>(ws, L.pay_a), *pb = at<Pay>(ws, L.pay_b);
   uint16_t* bdesc = at<uint16_t>(ws, L.bdesc);
   uint32_t* bent = at<uint32_t>(ws, L.bent);
   Seg* seg[2] = {at<Seg>(ws, L.seg_a), at<Seg>(ws, L.seg_b)};
   Work* work[2] = {at<Work>(ws, L.work_a), at<Work>(ws, L.work_b)};
-  uint32_t* hist = at<uint32_t>(ws, L.seg_hist);
-  uint32_t* cur = at<uint32_t>(ws, L.seg_cur);
-  Seg* giants = at<Seg>(ws, L.giants);
-  BucketCtl* ctl = bucket_ctl(ws, L);
+  uint32_t *hist = at<uint32_t>(ws, L.seg_hist), *cur = at<uint32_t>(ws, L.seg_cur);
+  Seg *giants = at<Seg>(ws, L.giants), *bigs = at<Seg>(ws, L.bigs);
+
+  Step(const StepCall& call, const StepSwitches& w, const Layout& lay, bool allow_bucket) : c(call), sw(w), L(lay) {
+    b.k1 = bitlen((uint64_t)kc.n_k1);
+    b.k2 = bitlen((uint64_t)kc.n_k2);
+    bucket = allow_bucket && b.k1 + b.k2 <= kMaxKeyBits && !sw.force_global_sort;
+    plannable = bucket && L.max_ent <= kEntHistMax && b.k1 >= kRadixBits && !sw.no_l1_plan;
+  }
+};
+
+// 1. entity runs.  The bucket descriptors (2 bytes per record, the step's largest fill) are zeroed
+// while the host waits for the entity count, when the first partition level will be planned.
+int count_stage(Step& S) {
+  const StepCall& c = S.c;
+  const bool prefill = S.plannable && !S.sw.no_prefill && S.n > 0;
+  FillBatch pre;
+  if (prefill) pre.add(S.bdesc, sizeof(uint16_t) * (size_t)S.n);
+  bool dup = false;
+  const CountOpts o{S.gene, true, c.plan->n_cell_ids, prefill ? &pre : nullptr};
+  if (int rc = count_runs(S.cell ? c.rec->cell : c.rec->gene, S.n, c.ws, S.L, o, &S.n_ent, &dup, S.s)) return rc;
+  if (dup) return fail(SCT_EINVAL, "grouped gene partials need cell-sorted records (a cell id forms two runs)");
+  if (S.n_ent > S.L.max_ent)
+    return fail(SCT_ENOMEM, "%lld entities exceed plan.max_entities %lld", (long long)S.n_ent, (long long)S.L.max_ent);
+  if (c.out_i && S.n_ent > c.capacity)
+    return fail(SCT_EINVAL, "%lld entities exceed output capacity %lld", (long long)S.n_ent, (long long)c.capacity);
+  S.planned = S.plannable && S.n_ent > 0;
+  S.use_side = S.planned && S.exact && !S.sw.no_side;
+  // SCT_STREAM_LANES=fused keeps the lanes in the key pass, and so does a call that finds another
+  // call's pair in use on the device (fork_lanes)
+  S.split = S.use_side && S.streams && S.n > 0 && !S.sw.lanes_fused;
+  if (S.planned)
+    S.l1 = L1Plan{at<uint32_t>(S.ws, S.L.ent_hist), at<uint32_t>(S.ws, S.L.l1_toff), at<uint2>(S.ws, S.L.l1_tslot),
+                  S.pb, S.sw.l1_bits};
+  return SCT_OK;
+}
+
+// 3. every buffer the step zeroes before its first kernel, in one launch
+int fills_stage(Step& S) {
+  const sct_plan_t* plan = S.c.plan;
+  FillBatch fb;
+  if (S.cell && !S.mito) {
+    uint8_t* z = at<uint8_t>(S.ws, S.L.zero_mito);
+    fb.add(z, (size_t)plan->n_gene_ids);
+    S.mito = z;
+  }
+  fb.add(S.partials, sizeof(int64_t) * SCT_NP * (size_t)S.n_ent);
+  if (S.gene) {
+    fb.add(S.gcounts, sizeof(uint32_t) * (size_t)S.L.n_buckets);
+    fb.add(S.c.gene_partials, sizeof(int64_t) * SCT_NP * (size_t)plan->n_gene_ids);  // (written by gene_reduce only)
+  }
+  fb.add(S.ctl, sizeof(BucketCtl));
+  fb.add(S.gwide, sizeof(uint32_t), S.streams ? 0 : 1);
+  if (S.planned) {  // the level-1 plan's buffers (bucket_level1_plan); bdesc unless count_stage zeroed it
+    if (S.sw.no_prefill) fb.add(S.bdesc, sizeof(uint16_t) * (size_t)S.n);
+    fb.add(S.ctr0, 3 * sizeof(uint32_t));
+    fb.add(S.l1.hist, sizeof(uint32_t) * kRadix * (size_t)S.n_ent);
+  }
+  return launch_fills(fb, S.s);
+}
+
+// 4. Round 8: on the planned bucket path with exact floats the quality-stream lanes run as a kernel
+// of their own (segment.h k_stream_lanes) on the pair's second stream, and the key pass without
+// them.  They fork here (the fills zeroed the partial rows and gwide): beside the level-1 plan and
+// its classification, which are latency-bound, and whatever is left beside the key pass.  (A fork
+// after the key pass, beside the partition levels >= 2, measured no gain: the early big buckets fill
+// that stretch)  A call that finds another call's pair in use on the device
+// keeps the one launch (the pool would then open further streams, and a process has 4 hardware
+// queues).
+int fork_lanes(Step& S) {
+  if (!S.split) return SCT_OK;
+  HIPCHK(S.st.open());
+  HIPCHK(S.st.fork(0, S.s));  // (the pair's first stream has forked here too since it was opened here)
+  S.split = S.st.alone;
+  if (!S.split) return SCT_OK;
+  HIPCHK(S.st.fork(1, S.s));
+  hipStream_t sp = S.st.use(1);
+  const dim3 tgrid((unsigned)cdiv(S.n, kKTile));
+  uint32_t* gw = S.gene ? S.gwide : nullptr;
+#define SCT_LANES(C) \
+  LAUNCH_N("stream_lanes", S.n, k_stream_lanes<C>, tgrid, dim3(kBlock), sp, S.rc, S.n, S.toff, S.hbits, S.partials, gw)
+  SCT_VIEW2(S.cell, SCT_LANES);
+#undef SCT_LANES
+  HIPCHK(S.st.mark(1, &S.lanes_done));
+  return SCT_OK;
+}
+
+// 5. The first partition level planned before the key pass (segment.h k_level1_plan): run ids and
+// per-entity digit counts, level 0, then level 1's classification with a grid sized for the most
+// segments there can be (the device count bounds it): l1.hist then holds every segment child's start.
+// No host wait: level 1's counts, final after its classification, are copied now and read by
+// bucket_distinct while the key pass runs (no host wait between the key pass and level 2).
+// (its buffers -- bdesc, the level-0 counters, l1.hist -- were zeroed by fills_stage)
+int bucket_level1_plan(Step& S) {
+  const Bits& b = S.b;
+  const int64_t n = S.n, n_ent = S.n_ent;
+  hipStream_t s = S.s;
   const int KB = b.k1 + b.k2 + b.h;
-  Seg* bigs = at<Seg>(ws, L.bigs);
-  int level = 1, c = 0;  // (each segment carries its own depth: bucket.h Seg)
-  if (planned) {
-    level = 2;
-    c = 1;
-  } else {
-    HIPCHK(hipMemsetAsync(bdesc, 0, sizeof(uint16_t) * (size_t)n, s));
-    HIPCHK(hipMemsetAsync(ctl, 0, offsetof(BucketCtl, err), s));  // keeps ctl->err from build_keys
-    HIPCHK(hipMemsetAsync(&ctl->n_big, 0, sizeof(uint32_t), s));
-    LAUNCH("bucket_level0", k_bucket_level0, dim3((unsigned)cdiv(n_ent, kBlock)), dim3(kBlock), s, ent_start, n_ent,
-           n, bdesc, bent, seg[0], work[0], bigs, ctl, &ctl->n_seg);
-  }
-  BucketCtl h{};
-  // planned: the level-1 counts were read back early (pipeline: queued before the key pass), so the
-  // host sizes level 2 while the key pass still runs; the key pass's error flag is read with the next
-  // level's counts (kernels before that stay in bounds: ids are clamped, ref ids masked)
-  bool err_pending = false;
-  if (planned) {
-    if (int rb = readback_finish(&h, sizeof(h))) return rb;
-    err_pending = true;
-  }
-  if (!planned || h.n_seg == 0) {
-    if (int rb = readback(&h, ctl, sizeof(h), s)) return rb;
-    err_pending = false;
-  }
-  const auto err_check = [&]() -> int {
-    if (h.err & 2) return fail(SCT_EINVAL, "a gene / cell / umi id lies outside its dictionary size");
-    return h.err ? 1 : SCT_OK;
-  };
-  if (!err_pending)
-    if (int e = err_check()) return e;
-  // Round 6: the big buckets of levels 0 and 1 (their records are final once the key pass has run)
-  // start on a side stream right away, beside levels >= 2, whose small partition kernels leave most
-  // CUs idle; the caller's stream waits for them after the hash-tile launch.  Big buckets, level
-  // segments and terminal buckets are disjoint record ranges, and the partial rows are summed
-  // with atomics, so the order between the streams does not matter.
-  const auto launch_big = [&](uint32_t cnt, const Seg* bg, hipStream_t st) -> int {
-    const dim3 bgrid(cnt);
-    const bool wide = b.k1 > kNarrowK1Bits;
-#define SCT_BIG(C, G, W) \
-  LAUNCH("big_bucket", (k_big_bucket<C, G, W>), bgrid, dim3(kBigBlock), st, bg, pa, pb, b, partials, dflags)
-    if (cell && gene) {
-      if (wide) { SCT_BIG(true, true, true); } else { SCT_BIG(true, true, false); }
-    } else if (cell) {
-      if (wide) { SCT_BIG(true, false, true); } else { SCT_BIG(true, false, false); }
-    } else {
-      if (wide) { SCT_BIG(false, false, true); } else { SCT_BIG(false, false, false); }
-    }
-#undef SCT_BIG
-    return SCT_OK;
-  };
-  const char* no_early = getenv("SCT_NO_EARLY_BIG");
-  const bool side_big = side.is_open() && !(no_early && no_early[0] == '1');
-  const bool early_big = side_big && h.n_big > 0 && h.n_seg > 0;
-  const char* no_late = getenv("SCT_NO_LEVEL_BIG");
-  uint32_t big_done = 0;
-  if (early_big) {
-    if (int r = launch_big(h.n_big, bigs, side.use())) return r;
-    big_done = h.n_big;
-  }
-  while (h.n_seg > 0) {
-    if ((int64_t)h.n_seg > L.max_seg || (int64_t)h.n_work > L.max_work)
-      return fail(SCT_ENOMEM, "bucket level %d: %u segments / %u work items exceed the workspace", level, h.n_seg,
-                  h.n_work);
-    const int src = (level - 1) & 1;
-    const Pay* pin = src ? pb : pa;
-    Pay* pout = src ? pa : pb;
-    HIPCHK(hipMemsetAsync(hist, 0, sizeof(uint32_t) * kRadix * (size_t)h.n_seg, s));
-    LAUNCH("bucket_hist", k_bucket_hist, dim3(h.n_work), dim3(kBlock), s, pin, (const Seg*)seg[c],
-           (const Work*)work[c], KB, hist);
-    HIPCHK(hipMemsetAsync(ctl, 0, 2 * sizeof(uint32_t), s));  // next level's n_seg, n_work
-    LAUNCH("bucket_classify", k_bucket_classify, dim3(h.n_seg), dim3(kBlock), s, (const Seg*)seg[c], hist, cur, 0,
-           b.k1, b.k1 + b.k2, KB, level & 1, 0, bdesc, bent, seg[c ^ 1], work[c ^ 1], giants, bigs, ctl,
-           (const uint32_t*)nullptr);
-    // the next level's counts are final after classify: read them while the scatter runs
-    if (int rb = readback_start(ctl, sizeof(h), s)) return rb;
-    const uint32_t n_work = h.n_work;
-    LAUNCH("bucket_scatter", k_bucket_scatter, dim3(n_work), dim3(kSBlock), s, pin, pout,
-           (const Seg*)seg[c], (const Work*)work[c], KB, cur);
-    if (int rb = readback_finish(&h, sizeof(h))) return rb;
-    if (err_pending) {
-      err_pending = false;
-      if (int e = err_check()) return e;
-    }
-    // this level's big buckets (written by its scatter) join the side stream when another level follows
-    if (side_big && h.n_seg > 0 && h.n_big > big_done && !(no_late && no_late[0] == '1')) {
-      HIPCHK(side.from_caller(s));
-      if (int r = launch_big(h.n_big - big_done, bigs + big_done, side.use())) return r;
-      big_done = h.n_big;
-    }
-    c ^= 1;
-    level++;
-  }
-  const dim3 tgrid((unsigned)cdiv(n, kWin));
-  // the early big buckets finish before the hash tiles start (SCT_BIG_BESIDE_HASH=1: they may run into
-  // them; the hash tiles' 40 KB blocks then hold every CU's LDS and the big buckets' 80 KB blocks wait)
-  const char* beside = getenv("SCT_BIG_BESIDE_HASH");
-  const bool join_first = big_done > 0 && !(beside && beside[0] == '1');
-  if (join_first) HIPCHK(side.to_caller(s));
-  int rc;
-  if (b.k1 > kNarrowK1Bits) {
-    rc = launch_hash_tile<true>(cell, gene, tgrid, s, bdesc, bent, pa, pb, n, b, partials, dflags);
-  } else {
-    rc = launch_hash_tile<false>(cell, gene, tgrid, s, bdesc, bent, pa, pb, n, b, partials, dflags);
-  }
-  if (rc) return rc;
-  // (round 4: the big buckets on a side stream beside the hash tiles measured the same step time,
-  // 5.26 ms either way, profiles/r04/e_l1fast_gbam_dicts/var/); round 6: those of levels 0-1 already
-  // run beside levels >= 2 (above), so only the later levels' big buckets are launched here
-  if (big_done > 0 && !join_first) HIPCHK(side.to_caller(s));
-  if (h.n_big > big_done) {
-    rc = launch_big(h.n_big - big_done, bigs + big_done, s);
-    if (rc) return rc;
-  }
-  if (h.n_giant > 0) {
-    const dim3 ggrid(h.n_giant);
-    if (cell && gene) {
-      LAUNCH("bucket_giant", (k_bucket_giant<true, true>), ggrid, dim3(kBlock), s, (const Seg*)giants, pa, pb,
-             partials, dflags);
-    } else if (cell) {
-      LAUNCH("bucket_giant", (k_bucket_giant<true, false>), ggrid, dim3(kBlock), s, (const Seg*)giants, pa, pb,
-             partials, dflags);
-    } else {
-      LAUNCH("bucket_giant", (k_bucket_giant<false, false>), ggrid, dim3(kBlock), s, (const Seg*)giants, pa, pb,
-             partials, dflags);
-    }
-  }
-  return SCT_OK;
+  LAUNCH_N("level1_plan", n, k_level1_plan, dim3((unsigned)cdiv(n, kKTile)), dim3(kBlock), s, S.hbits,
+           S.kc.k1, S.kc.n_k1, n, S.toff, b, S.ent_start, S.l1);
+  LAUNCH("bucket_level0", k_bucket_level0, dim3((unsigned)cdiv(n_ent, kBlock)), dim3(kBlock), s,
+         S.ent_start, n_ent, n, S.bdesc, S.bent, S.seg[0], S.work[0], S.bigs, S.ctl, S.ctr0);
+  const int64_t max_seg = n_ent < n / (kBigCap + 1) + 1 ? n_ent : n / (kBigCap + 1) + 1;
+  if (max_seg > S.L.max_seg) return fail(SCT_ENOMEM, "level 1: %lld segments exceed the workspace", (long long)max_seg);
+  LAUNCH("bucket_classify", k_bucket_classify, dim3((unsigned)max_seg), dim3(kBlock), s, (const Seg*)S.seg[0],
+         S.l1.hist, S.cur, S.l1.bits, b.k1, b.k1 + b.k2, KB, 1, 1, S.bdesc, S.bent, S.seg[1], S.work[1], S.giants,
+         S.bigs, S.ctl, (const uint32_t*)S.ctr0);
+  return readback_start(S.ctl, sizeof(BucketCtl), s);
 }
 
-// The RUN-mode pipeline (entity = runs of the cell column, or of the gene column in gene
-// mode; GROUPED runs the cell view).  Writes partial rows into the workspace, output rows
-// if out_i / out_f are set, and grouped gene partials (cell view) if gene_partials is set.
-template <bool kBucket, bool kStreams>
-int launch_build_keys(bool cell, bool gene, dim3 grid, hipStream_t s, const KeyCols& kc, const RecCols& rc2,
-                      const uint8_t* mito, int64_t n, const uint64_t* toff, const Bits& b, uint64_t* keys,
-                      void* vals, const uint64_t* head_bits, const int64_t* ent_start, int64_t* partials,
-                      uint32_t* gcounts, int n_buckets,
-                      uint32_t* err, uint32_t* gwide, uint32_t* gtoff, const L1Plan& l1) {
-  if (cell && gene) {
-    LAUNCH_SHM_N("build_keys", n, (k_build_keys_run<true, true, kBucket, kStreams>), grid, dim3(kBlock),
-               sizeof(uint32_t) * (size_t)n_buckets, s, kc, rc2, mito, n, toff, b, keys, vals, head_bits, ent_start, partials,
-               gcounts, n_buckets, err, gwide, gtoff, l1);
-  } else if (cell) {
-    LAUNCH_N("build_keys", n, (k_build_keys_run<true, false, kBucket, kStreams>), grid, dim3(kBlock), s, kc, rc2, mito, n,
-           toff, b, keys, vals, head_bits, ent_start, partials, gcounts, n_buckets, err, gwide, gtoff, l1);
-  } else {
-    LAUNCH_N("build_keys", n, (k_build_keys_run<false, false, kBucket, kStreams>), grid, dim3(kBlock), s, kc, rc2, mito,
-           n, toff, b, keys, vals, head_bits, ent_start, partials, gcounts, n_buckets, err, gwide, gtoff, l1);
-  }
-  return SCT_OK;
-}
-
-// Sequential Welford (SCT_FLOAT_WELFORD): big entities one wave each (largest first), small ones a
-// lane each.  It needs only the entity starts, the input columns and its own workspace, and writes
-// only the mean / variance slots of the output rows (k_finalize writes the others), so it runs on a
-// side stream from the moment the entity starts exist, beside the key pass' successors (bucket
-// partition, hash tiles) on the caller's stream.
-// The side streams come from a per-device pool of (s2, s3) pairs created once and reused (round 4:
-// creating them per call cost ~0.6 ms of host time before the first Welford launch).  A call holds
-// its pair until it returns, so concurrent pipelines on one device get pairs of their own (round 5:
-// a shared pair queued one pipeline's head kernel behind another's, and the start gate then held
-// the second pipeline's key pass for its whole time-out).
-constexpr int kMaxSideDevices = 64;
-struct SidePool {
-  std::mutex mu;
-  std::vector<std::pair<hipStream_t, hipStream_t>> free[kMaxSideDevices];
-  int in_use[kMaxSideDevices] = {};  // pairs held by running calls, per device
-};
-SidePool& side_pool() {
-  static SidePool p;
-  return p;
-}
-// *alone: no other call on this device holds a pair (so no other pipeline's Welford kernels can
-// share a hardware queue with this one's)
-hipError_t side_streams(int dev, hipStream_t* s2, hipStream_t* s3, bool* alone) {  // (`dev` is current)
-  if (dev < 0 || dev >= kMaxSideDevices) return hipErrorInvalidDevice;
-  SidePool& p = side_pool();
-  {
-    std::lock_guard<std::mutex> g(p.mu);
-    *alone = p.in_use[dev] == 0;
-    if (!p.free[dev].empty()) {
-      *s2 = p.free[dev].back().first;
-      *s3 = p.free[dev].back().second;
-      p.free[dev].pop_back();
-      p.in_use[dev]++;
-      return hipSuccess;
-    }
-  }
-  hipStream_t a = nullptr, b = nullptr;
-  hipError_t e = hipStreamCreateWithFlags(&a, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&b, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    if (a) (void)hipStreamDestroy(a);
-    return e;
-  }
-  *s2 = a;
-  *s3 = b;
-  std::lock_guard<std::mutex> g(p.mu);
-  p.in_use[dev]++;
-  return hipSuccess;
-}
-void side_streams_release(int dev, hipStream_t s2, hipStream_t s3) {
-  SidePool& p = side_pool();
-  std::lock_guard<std::mutex> g(p.mu);
-  p.free[dev].emplace_back(s2, s3);
-  p.in_use[dev]--;
-}
-struct WelfordSide {
-  int dev = -1;
-  hipStream_t s2 = nullptr, s3 = nullptr;
-  hipEvent_t fork = nullptr, join = nullptr, fork3 = nullptr, join3 = nullptr;
-  ~WelfordSide() {  // the caller's stream waits on `join` and `join3` before anything after the pipeline
-    if (fork) (void)hipEventDestroy(fork);
-    if (join) (void)hipEventDestroy(join);
-    if (fork3) (void)hipEventDestroy(fork3);
-    if (join3) (void)hipEventDestroy(join3);
-    if (s2) side_streams_release(dev, s2, s3);  // (work still queued on them stays in order)
-  }
-};
-
-int welford_stage(const Layout& L, void* ws, bool cell, int64_t n, int64_t n_ent, const RecCols& rc2,
-                  const int64_t* ent_start, double* out_f, hipStream_t s, WelfordSide& wf) {
-  // the side stream lives on the caller's stream's device (the calling thread's current device
-  // may be another one)
-  int dev = 0, prev = 0;
-  HIPCHK(hipStreamGetDevice(s, &dev));
-  HIPCHK(hipGetDevice(&prev));
-  if (prev != dev) HIPCHK(hipSetDevice(dev));
-  bool alone = true;
-  hipError_t ce = side_streams(dev, &wf.s2, &wf.s3, &alone);
-  if (ce == hipSuccess) wf.dev = dev;
-  if (ce == hipSuccess) ce = hipEventCreateWithFlags(&wf.fork, hipEventDisableTiming);
-  if (ce == hipSuccess) ce = hipEventCreateWithFlags(&wf.join, hipEventDisableTiming);
-  if (ce == hipSuccess) ce = hipEventCreateWithFlags(&wf.fork3, hipEventDisableTiming);
-  if (ce == hipSuccess) ce = hipEventCreateWithFlags(&wf.join3, hipEventDisableTiming);
-  if (prev != dev) HIPCHK(hipSetDevice(prev));
-  HIPCHK(ce);
-  HIPCHK(hipEventRecord(wf.fork, s));
-  HIPCHK(hipStreamWaitEvent(wf.s2, wf.fork, 0));
-  hipStream_t s2 = wf.s2, s3 = wf.s3;
+// 6 / 8. Sequential Welford (SCT_FLOAT_WELFORD): big entities one wave each (largest first), small
+// ones a lane each.  It needs only the entity starts, the input columns and its own workspace, and
+// writes only the mean / variance slots of the output rows (k_finalize writes the others), so it runs
+// on the side streams from the moment the entity starts exist, beside the key pass' successors
+// (bucket partition, hash tiles) on the caller's stream: the head kernels on s2, the rest on s3.
+// finalize_stage joins both.
+int welford_stage(Step& S) {
+  const Layout& L = S.L;
+  void* ws = S.ws;
+  const int64_t n = S.n, n_ent = S.n_ent;
+  const int64_t* ent_start = S.ent_start;
+  double* out_f = S.c.out_f;
+  StepStreams& st = S.st;
+  HIPCHK(st.open());
+  HIPCHK(st.fork(0, S.s));
+  hipStream_t s = S.s, s2 = st.use(0), s3 = st.use(1);
   const dim3 egrid((unsigned)cdiv(n_ent, kBlock));
   if (n >= kWfWave) {
     WelfordCtl* wc = at<WelfordCtl>(ws, L.wctl);
@@ -614,8 +481,8 @@ int welford_stage(const Layout& L, void* ws, bool cell, int64_t n, int64_t n_ent
     LAUNCH("welford_order", k_welford_order, egrid, dim3(kBlock), s2, ent_start, n_ent, n, wc, worder);
     LAUNCH("welford_split", k_welford_split, dim3(1), dim3(kWave), s2, wc, wch);
     // the rest on s3: every record's samples, then the other groups' chains and the small entities
-    HIPCHK(hipEventRecord(wf.fork3, s2));
-    HIPCHK(hipStreamWaitEvent(s3, wf.fork3, 0));
+    hipEvent_t split_done = nullptr;
+    HIPCHK(st.fork(1, s2, &split_done));
     double* xs = at<double>(ws, L.wx);
     const dim3 xgrid((unsigned)cdiv(n, kBlock));
     const dim3 hgrid((unsigned)kWfBlocks);
@@ -631,320 +498,295 @@ int welford_stage(const Layout& L, void* ws, bool cell, int64_t n, int64_t n_ent
     // pipeline's gate could wait on CUs another pipeline holds).
     const uint32_t* started = &wch->started;
     constexpr unsigned kHeadBlocks = (unsigned)(kWfHeadEnts / kW2Ents);
-    const char* nogate = getenv("SCT_NO_WF_GATE");
-    const bool gate = alone && !(nogate && nogate[0] == '1');
-    if (cell) {
-      LAUNCH("welford_x_head", k_welford_x_ents<true>, hgrid, dim3(kBlock), s2, rc2, ent_start, n_ent, n,
-             (const uint32_t*)worder, (const WelfordCtl*)wch, xs);
-      LAUNCH_N("welford_head", n, k_welford_head2<true>, dim3(kHeadBlocks), dim3(kW2Waves * kWave), s2, ent_start,
-               n_ent, n, (const uint32_t*)worder, wch, (const double*)xs, out_f);
-    } else {
-      LAUNCH("welford_x_head", k_welford_x_ents<false>, hgrid, dim3(kBlock), s2, rc2, ent_start, n_ent, n,
-             (const uint32_t*)worder, (const WelfordCtl*)wch, xs);
-      LAUNCH_N("welford_head", n, k_welford_head2<false>, dim3(kHeadBlocks), dim3(kW2Waves * kWave), s2, ent_start,
-               n_ent, n, (const uint32_t*)worder, wch, (const double*)xs, out_f);
-    }
+    const bool gate = st.alone && !S.sw.no_wf_gate;
+#define SCT_WF_HEAD(C)                                                                                            \
+  LAUNCH("welford_x_head", k_welford_x_ents<C>, hgrid, dim3(kBlock), s2, S.rc, ent_start, n_ent, n,               \
+         (const uint32_t*)worder, (const WelfordCtl*)wch, xs);                                                    \
+  LAUNCH_N("welford_head", n, k_welford_head2<C>, dim3(kHeadBlocks), dim3(kW2Waves * kWave), s2, ent_start, n_ent, \
+           n, (const uint32_t*)worder, wch, (const double*)xs, out_f)
+    SCT_VIEW2(S.cell, SCT_WF_HEAD);
+#undef SCT_WF_HEAD
     if (gate) {
-      HIPCHK(hipStreamWaitEvent(s, wf.fork3, 0));
+      HIPCHK(st.wait_caller(split_done));
       LAUNCH("welford_gate", k_wf_gate, dim3(1), dim3(kWave), s, started, kHeadBlocks, kWfGateTicks);
       LAUNCH("welford_gate", k_wf_gate, dim3(1), dim3(kWave), s3, started, kHeadBlocks, kWfGateTicks);
     }
-    if (cell) {
-      LAUNCH_N("welford_x", n, k_welford_x<true>, xgrid, dim3(kBlock), s3, rc2, n, xs, ent_start, n_ent,
-               (const uint32_t*)worder, (const uint32_t*)&wch->n_big);
-      LAUNCH_N("welford_chains", n, k_welford_chains<true>, dim3(kWfBlocks), dim3(kBlock), s3, ent_start, n_ent, n,
-               (const uint32_t*)worder, wc, (const double*)xs, out_f);
-    } else {
-      LAUNCH_N("welford_x", n, k_welford_x<false>, xgrid, dim3(kBlock), s3, rc2, n, xs, ent_start, n_ent,
-               (const uint32_t*)worder, (const uint32_t*)&wch->n_big);
-      LAUNCH_N("welford_chains", n, k_welford_chains<false>, dim3(kWfBlocks), dim3(kBlock), s3, ent_start, n_ent, n,
-               (const uint32_t*)worder, wc, (const double*)xs, out_f);
-    }
+#define SCT_WF_REST(C)                                                                                           \
+  LAUNCH_N("welford_x", n, k_welford_x<C>, xgrid, dim3(kBlock), s3, S.rc, n, xs, ent_start, n_ent,               \
+           (const uint32_t*)worder, (const uint32_t*)&wch->n_big);                                               \
+  LAUNCH_N("welford_chains", n, k_welford_chains<C>, dim3(kWfBlocks), dim3(kBlock), s3, ent_start, n_ent, n,     \
+           (const uint32_t*)worder, wc, (const double*)xs, out_f)
+    SCT_VIEW2(S.cell, SCT_WF_REST);
+#undef SCT_WF_REST
   } else {
-    HIPCHK(hipEventRecord(wf.fork3, s2));
-    HIPCHK(hipStreamWaitEvent(s3, wf.fork3, 0));
+    HIPCHK(st.fork(1, s2));
   }
-  if (cell) {
-    LAUNCH("welford", k_welford<true>, egrid, dim3(kBlock), s3, rc2, ent_start, n_ent, n, out_f);
-  } else {
-    LAUNCH("welford", k_welford<false>, egrid, dim3(kBlock), s3, rc2, ent_start, n_ent, n, out_f);
+#define SCT_WF(C) LAUNCH("welford", k_welford<C>, egrid, dim3(kBlock), s3, S.rc, ent_start, n_ent, n, out_f)
+  SCT_VIEW2(S.cell, SCT_WF);
+#undef SCT_WF
+  return SCT_OK;
+}
+
+// 7. input order: runs, keys, additive metrics (+ gene-bucket counts per tile; kStreams: + the lanes)
+template <bool kBucket, bool kStreams>
+int launch_build_keys(Step& S) {
+  const dim3 tgrid((unsigned)cdiv(S.n, kKTile));
+  uint64_t* keys = S.B.ka;  // (the bucket path writes Pay records through `keys`: the same buffer)
+  void* vals = kBucket ? nullptr : (void*)S.B.va;
+  const size_t shm = sizeof(uint32_t) * (size_t)S.L.n_buckets;  // the gene view's bucket counts
+#define SCT_KEYS(C, G)                                                                                            \
+  LAUNCH_SHM_N("build_keys", S.n, (k_build_keys_run<C, G, kBucket, kStreams>), tgrid, dim3(kBlock), (G) ? shm : 0, \
+               S.s, S.kc, S.rc, S.mito, S.n, S.toff, S.b, keys, vals, S.hbits, S.ent_start, S.partials, S.gcounts, \
+               S.L.n_buckets, &S.ctl->err, S.gwide, S.gtoff, S.l1)
+  SCT_VIEW3(S.cell, S.gene, SCT_KEYS);
+#undef SCT_KEYS
+  return SCT_OK;
+}
+int key_pass(Step& S) {
+  const bool lanes = S.streams && !S.split;
+  if (S.bucket) return lanes ? launch_build_keys<true, true>(S) : launch_build_keys<true, false>(S);
+  if (int rc = lanes ? launch_build_keys<false, true>(S) : launch_build_keys<false, false>(S)) return rc;
+  uint32_t err = 0;  // the bucket path reads the flag at its first level sync
+  if (int rb = readback(&err, &S.ctl->err, sizeof(err), S.s)) return rb;
+  if (err & 2) return fail(SCT_EINVAL, "a gene / cell / umi id lies outside its dictionary size");
+  return SCT_OK;
+}
+
+// 9. Round 6: a side stream forked after the key pass (planned bucket path, exact floats) runs the
+// gene view's plan and the big buckets of levels 0-1 beside the partition levels >= 2 and the
+// hash tiles, and the cell rows' finalize beside the gene view
+int launch_gene_plan(Step& S, hipStream_t on) {
+  LAUNCH_SHM("gene_plan", k_gene_plan, dim3(1), dim3(kBlock), 2 * sizeof(uint32_t) * (size_t)(S.L.n_buckets + 1), on,
+             (const uint32_t*)S.gcounts, S.L.n_buckets, S.gcur, S.gwork, S.n_gwork);
+  return SCT_OK;
+}
+int fork_side(Step& S) {
+  if (!S.use_side) return SCT_OK;
+  HIPCHK(S.st.open());
+  HIPCHK(S.st.fork(0, S.s));
+  if (!S.gene) return SCT_OK;
+  if (int rc = launch_gene_plan(S, S.st.use(0))) return rc;
+  HIPCHK(S.st.mark(0, &S.plan_done));
+  return SCT_OK;
+}
+
+int launch_big(Step& S, uint32_t cnt, const Seg* bg, hipStream_t st) {
+  const dim3 bgrid(cnt);
+#define SCT_BIG(C, G, W) \
+  LAUNCH("big_bucket", (k_big_bucket<C, G, W>), bgrid, dim3(kBigBlock), st, bg, S.pa, S.pb, S.b, S.partials, S.dflags)
+  if (S.b.k1 > kNarrowK1Bits) SCT_VIEW3(S.cell, S.gene, SCT_BIG, true);
+  else SCT_VIEW3(S.cell, S.gene, SCT_BIG, false);
+#undef SCT_BIG
+  return SCT_OK;
+}
+
+// 10, bucket path (bucket.h): level 0 classification, MSD levels until no segment exceeds kBCap,
+// then the hash-tile pass (+ giants).  One host wait per level to size the next level's launches,
+// for a copy queued right after the classification: the level's scatter runs meanwhile.
+// planned: level 0 and level 1 ran before the key pass (bucket_level1_plan), and the key pass wrote
+// the level-1 children: the loop starts at level 2.
+// Returns kRedoGlobalSort (not an error code) when build_keys saw a mapped ref id the payload cannot
+// hold: the caller then reruns on the global-sort path.
+constexpr int kRedoGlobalSort = 1;
+int bucket_distinct(Step& S) {
+  const Layout& L = S.L;
+  const Bits& b = S.b;
+  const int64_t n = S.n;
+  hipStream_t s = S.s;
+  StepStreams& st = S.st;
+  BucketCtl* ctl = S.ctl;
+  if (n == 0) return SCT_OK;
+  const int KB = b.k1 + b.k2 + b.h;
+  int level = S.planned ? 2 : 1, c = S.planned ? 1 : 0;  // (each segment carries its own depth: bucket.h Seg)
+  if (!S.planned) {
+    HIPCHK(hipMemsetAsync(S.bdesc, 0, sizeof(uint16_t) * (size_t)n, s));
+    HIPCHK(hipMemsetAsync(ctl, 0, offsetof(BucketCtl, err), s));  // keeps ctl->err from build_keys
+    HIPCHK(hipMemsetAsync(&ctl->n_big, 0, sizeof(uint32_t), s));
+    LAUNCH("bucket_level0", k_bucket_level0, dim3((unsigned)cdiv(S.n_ent, kBlock)), dim3(kBlock), s,
+           S.ent_start, S.n_ent, n, S.bdesc, S.bent, S.seg[0], S.work[0], S.bigs, ctl, &ctl->n_seg);
+  }
+  BucketCtl h{};
+  // planned: the level-1 counts were read back early (bucket_level1_plan: queued before the key pass),
+  // so the host sizes level 2 while the key pass still runs; the key pass's error flag is read with the
+  // next level's counts (kernels before that stay in bounds: ids are clamped, ref ids masked)
+  bool err_pending = false;
+  if (S.planned) {
+    if (int rb = readback_finish(&h, sizeof(h))) return rb;
+    err_pending = true;
+  }
+  if (!S.planned || h.n_seg == 0) {
+    if (int rb = readback(&h, ctl, sizeof(h), s)) return rb;
+    err_pending = false;
+  }
+  const auto err_check = [&]() -> int {
+    if (h.err & 2) return fail(SCT_EINVAL, "a gene / cell / umi id lies outside its dictionary size");
+    return h.err ? kRedoGlobalSort : SCT_OK;
+  };
+  if (!err_pending)
+    if (int e = err_check()) return e;
+  // Round 6: the big buckets of levels 0 and 1 (their records are final once the key pass has run)
+  // start on the side stream right away, beside levels >= 2, whose small partition kernels leave most
+  // CUs idle; the caller's stream waits for them after the hash-tile launch.  Big buckets, level
+  // segments and terminal buckets are disjoint record ranges, and the partial rows are summed
+  // with atomics, so the order between the streams does not matter.
+  const bool side_big = S.use_side && !S.sw.no_early_big;
+  const bool early_big = side_big && h.n_big > 0 && h.n_seg > 0;
+  uint32_t big_done = 0;
+  if (early_big) {
+    if (int r = launch_big(S, h.n_big, S.bigs, st.use(0))) return r;
+    big_done = h.n_big;
+  }
+  while (h.n_seg > 0) {
+    if ((int64_t)h.n_seg > L.max_seg || (int64_t)h.n_work > L.max_work)
+      return fail(SCT_ENOMEM, "bucket level %d: %u segments / %u work items exceed the workspace", level, h.n_seg,
+                  h.n_work);
+    const int src = (level - 1) & 1;
+    const Pay* pin = src ? S.pb : S.pa;
+    Pay* pout = src ? S.pa : S.pb;
+    HIPCHK(hipMemsetAsync(S.hist, 0, sizeof(uint32_t) * kRadix * (size_t)h.n_seg, s));
+    LAUNCH("bucket_hist", k_bucket_hist, dim3(h.n_work), dim3(kBlock), s, pin, (const Seg*)S.seg[c],
+           (const Work*)S.work[c], KB, S.hist);
+    HIPCHK(hipMemsetAsync(ctl, 0, 2 * sizeof(uint32_t), s));  // next level's n_seg, n_work
+    LAUNCH("bucket_classify", k_bucket_classify, dim3(h.n_seg), dim3(kBlock), s, (const Seg*)S.seg[c], S.hist, S.cur,
+           0, b.k1, b.k1 + b.k2, KB, level & 1, 0, S.bdesc, S.bent, S.seg[c ^ 1], S.work[c ^ 1], S.giants, S.bigs, ctl,
+           (const uint32_t*)nullptr);
+    // the next level's counts are final after classify: read them while the scatter runs
+    if (int rb = readback_start(ctl, sizeof(h), s)) return rb;
+    const uint32_t n_work = h.n_work;
+    LAUNCH("bucket_scatter", k_bucket_scatter, dim3(n_work), dim3(kSBlock), s, pin, pout, (const Seg*)S.seg[c],
+           (const Work*)S.work[c], KB, S.cur);
+    if (int rb = readback_finish(&h, sizeof(h))) return rb;
+    if (err_pending) {
+      err_pending = false;
+      if (int e = err_check()) return e;
+    }
+    // this level's big buckets (written by its scatter) join the side stream when another level follows
+    if (side_big && h.n_seg > 0 && h.n_big > big_done && !S.sw.no_level_big) {
+      HIPCHK(st.fork(0, s));
+      if (int r = launch_big(S, h.n_big - big_done, S.bigs + big_done, st.use(0))) return r;
+      big_done = h.n_big;
+    }
+    c ^= 1;
+    level++;
+  }
+  const dim3 tgrid((unsigned)cdiv(n, kWin));
+  // the early big buckets finish before the hash tiles start (SCT_BIG_BESIDE_HASH=1: they may run into
+  // them; the hash tiles' 40 KB blocks then hold every CU's LDS and the big buckets' 80 KB blocks wait)
+  const bool join_first = big_done > 0 && !S.sw.big_beside_hash;
+  if (join_first) HIPCHK(st.join(0));
+#define SCT_HASH(C, G, W)                                                                                     \
+  LAUNCH_N("hash_tile", n, (k_hash_tile<C, G, W>), tgrid, dim3(kHBlock), s, S.bdesc, S.bent, S.pa, S.pb, n, b, \
+           S.partials, S.dflags)
+  if (b.k1 > kNarrowK1Bits) SCT_VIEW3(S.cell, S.gene, SCT_HASH, true);
+  else SCT_VIEW3(S.cell, S.gene, SCT_HASH, false);
+#undef SCT_HASH
+  // (round 4: the big buckets on a side stream beside the hash tiles measured the same step time,
+  // 5.26 ms either way, profiles/r04/e_l1fast_gbam_dicts/var/); round 6: those of levels 0-1 already
+  // run beside levels >= 2 (above), so only the later levels' big buckets are launched here
+  if (big_done > 0 && !join_first) HIPCHK(st.join(0));
+  if (h.n_big > big_done)
+    if (int rc = launch_big(S, h.n_big - big_done, S.bigs + big_done, s)) return rc;
+  if (h.n_giant > 0) {
+    const dim3 ggrid(h.n_giant);
+#define SCT_GIANT(C, G) \
+  LAUNCH("bucket_giant", (k_bucket_giant<C, G>), ggrid, dim3(kBlock), s, S.giants, S.pa, S.pb, S.partials, S.dflags)
+    SCT_VIEW3(S.cell, S.gene, SCT_GIANT);
+#undef SCT_GIANT
   }
   return SCT_OK;
 }
 
-int pipeline(const sct_plan_t* plan, const sct_records_t* rec, const uint8_t* gene_is_mito, void* ws,
-             size_t ws_bytes, int64_t* out_i, double* out_f, int64_t capacity, int64_t* n_rows,
-             int64_t* gene_partials, hipStream_t s, bool allow_bucket = true) {
-  const Layout L = layout_for(plan);
-  if (!ws || ws_bytes < L.total) return fail(SCT_ENOMEM, "workspace too small (%zu < %zu)", ws_bytes, L.total);
-  const int64_t n = rec->n;
-  const bool cell = plan->mode != SCT_MODE_GENE;
-  const bool gene = gene_partials != nullptr;
-  const bool exact = plan->float_mode == SCT_FLOAT_EXACT_SUM;
-  const int32_t* ent_col = cell ? rec->cell : rec->gene;
+// 10, global-sort path: LSD radix sort of (key, record index), then one pass over the sorted keys
+int sorted_distinct(Step& S) {
+  int which = 0;
+  if (int rc = radix_sort(S.B, S.n, S.used + S.b.h, &which, S.s)) return rc;
+  const uint64_t* keys = which ? S.B.kb : S.B.ka;
+  const uint32_t* vals = which ? S.B.vb : S.B.va;
+  const dim3 rgrid((unsigned)cdiv(S.n, kReduceTile));
+#define SCT_REDUCE(C, G)                                                                                         \
+  LAUNCH_N("reduce_sorted", S.n, (k_reduce_sorted<C, G>), rgrid, dim3(kBlock), S.s, keys, vals, S.n, S.rc, S.mito, \
+           S.b, S.partials, S.dflags)
+  SCT_VIEW3(S.cell, S.gene, SCT_REDUCE);
+#undef SCT_REDUCE
+  return SCT_OK;
+}
 
-  int64_t n_ent = 0;
-  bool dup = false;
-  // the bucket descriptors (2 bytes per record, the step's largest fill) are zeroed while the host
-  // waits for the entity count, when the first partition level will be planned (below)
-  const char* nol1 = getenv("SCT_NO_L1_PLAN");
-  const char* force = getenv("SCT_FORCE_GLOBAL_SORT");
-  const char* nopre = getenv("SCT_NO_PREFILL");
-  const int k1_bits = bitlen((uint64_t)(cell ? plan->n_gene_ids : plan->n_cell_ids));
-  const bool may_plan = allow_bucket && k1_bits + bitlen((uint64_t)plan->n_umi_ids) <= kMaxKeyBits &&
-                        !(force && force[0] == '1') && L.max_ent <= kEntHistMax && k1_bits >= kRadixBits &&
-                        !(nol1 && nol1[0] == '1') && !(nopre && nopre[0] == '1') && n > 0;
-  FillBatch pre;
-  if (may_plan) pre.add(at<uint16_t>(ws, L.bdesc), sizeof(uint16_t) * (size_t)n);
-  int rc = count_runs(ent_col, n, ws, L, gene, plan->n_cell_ids, &n_ent, &dup, s, may_plan ? &pre : nullptr, true);
-  if (rc) return rc;
-  if (dup) return fail(SCT_EINVAL, "grouped gene partials need cell-sorted records (a cell id forms two runs)");
-  if (n_ent > L.max_ent)
-    return fail(SCT_ENOMEM, "%lld entities exceed plan.max_entities %lld", (long long)n_ent, (long long)L.max_ent);
-  if (out_i && n_ent > capacity)
-    return fail(SCT_EINVAL, "%lld entities exceed output capacity %lld", (long long)n_ent, (long long)capacity);
+// 12. partial rows -> output rows, beside the gene view when there is a side stream; the Welford
+// streams (welford_stage) are joined here
+int finalize_stage(Step& S) {
+  if (!S.c.out_i) return SCT_OK;
+  const bool side_fin = S.use_side && S.gene && !S.sw.no_side_fin;
+  if (side_fin) HIPCHK(S.st.fork(0, S.s));
+  hipStream_t fs = side_fin ? S.st.use(0) : S.s;
+  LAUNCH("finalize", k_finalize, dim3((unsigned)cdiv(S.n_ent * kFinThreads, kBlock)), dim3(kBlock), fs,
+         (const int64_t*)S.partials, S.n_ent, S.cell ? SCT_MODE_CELL : SCT_MODE_GENE, S.exact ? 1 : 0,
+         S.ent_start, S.c.out_i, S.c.out_f);
+  if (!S.exact) {
+    HIPCHK(S.st.join(0));
+    HIPCHK(S.st.join(1));
+  }
+  return SCT_OK;
+}
 
-  // key bits.  Bucket path (default): [k1' | k2 | hash], KB <= kMaxKeyBits, entities implied by
-  // the record ranges.  Global-sort path: [run | k1' | k2 | hash], padded to whole radix digits.
-  Bits b;
-  b.k1 = bitlen((uint64_t)(cell ? plan->n_gene_ids : plan->n_cell_ids));
-  b.k2 = bitlen((uint64_t)plan->n_umi_ids);
-  const bool bucket = allow_bucket && b.k1 + b.k2 <= kMaxKeyBits && !(force && force[0] == '1');
-  int used;
-  if (bucket) {
-    b.e = 0;
-    used = b.k1 + b.k2;
-    b.h = kMaxKeyBits - used < 8 ? kMaxKeyBits - used : 8;
-  } else {
-    b.e = bitlen((uint64_t)n_ent);
-    used = b.e + b.k1 + b.k2;
-    if (used > 63) return fail(SCT_EINVAL, "packed key needs %d bits (> 63)", used);
-    // fill the last radix digit with fragment-hash bits (same pass count), every shift < 64
-    const int padded = ((used + kRadixBits - 1) / kRadixBits) * kRadixBits;
-    b.h = (padded > 63 ? 63 : padded) - used;
-    if (b.h > 32) b.h = 32;
-  }
-  if (b.k1 > 0) {  // spread neighbouring k1 ids over the top key digits (odd multiplier, bijective)
-    b.mul = 0x9E3779B1u & b.k1_mask();
-    b.mul |= 1u;
-    uint32_t inv = b.mul;  // Newton: inverse mod 2^32, then mod 2^k1
-    for (int it = 0; it < 5; it++) inv *= 2u - b.mul * inv;
-    b.inv = inv & b.k1_mask();
-  }
+// 13. gene view: bucket starts, payload emission (input order), bucket reduction
+int gene_stage(Step& S) {
+  if (!S.gene) return SCT_OK;
+  const Layout& L = S.L;
+  const int64_t n = S.n;
+  void* gpay = at<GenePayload>(S.ws, L.gpay);
+  if (S.plan_done) HIPCHK(S.st.wait_caller(S.plan_done));
+  else if (int rc = launch_gene_plan(S, S.s)) return rc;
+  static_assert(kEmitTile == kKTile, "gene_emit tiles are the key pass's tiles (gtoff)");
+  const int staged = L.n_buckets <= kEmitStagedBuckets ? 1 : 0;
+  LAUNCH_SHM_N("gene_emit", n, k_gene_emit, dim3((unsigned)cdiv(n, kEmitTile)), dim3(kBlock),
+               (staged ? 3 : 2) * sizeof(uint32_t) * (size_t)L.n_buckets, S.s, S.c.rec->gene, S.rc,
+               (const uint16_t*)S.dflags, n, (const uint32_t*)S.gcur, (const uint32_t*)S.gtoff, L.n_buckets,
+               (const uint32_t*)S.gwide, staged, gpay);
+  LAUNCH_N("gene_reduce", n, k_gene_reduce, dim3((unsigned)L.max_gene_work), dim3(kBlock), S.s, (const void*)gpay,
+           (const int64_t*)S.gwork, (const int64_t*)S.n_gwork, S.c.plan->n_gene_ids, (const uint32_t*)S.gwide,
+           S.c.gene_partials);
+  return SCT_OK;
+}
 
-  KeyCols kc{cell ? rec->gene : rec->cell, rec->umi, (uint32_t)(cell ? plan->n_gene_ids : plan->n_cell_ids),
-             (uint32_t)plan->n_umi_ids};
-  RecCols rc2{rec->ref, rec->pos, rec->gq_sum, rec->gq_len, rec->gq_gt30, rec->bits, rec->xf,
-              rec->cy_gt30, rec->cy_len, rec->uy_gt30, rec->uy_len};
-  SortBuffers B{at<uint64_t>(ws, L.pay_a), at<uint64_t>(ws, L.pay_b), at<uint32_t>(ws, L.pay_a + L.half),
-                at<uint32_t>(ws, L.pay_b + L.half), at<uint32_t>(ws, L.counts), at<uint32_t>(ws, L.offsets),
-                at<uint64_t>(ws, L.scan_sums), L.count_cap};
-  // run heads (one bit per record) and entity starts (+ the sentinel ent_start[n_ent] = n): count_runs
-  const uint64_t* hbits = at<uint64_t>(ws, L.head_bits);
-  const int64_t* ent_start = at<int64_t>(ws, L.ent_start);
-  int64_t* partials = at<int64_t>(ws, L.partials);
-  uint32_t* gcounts = gene ? at<uint32_t>(ws, L.gcounts) : nullptr;
-  uint32_t* gtoff = gene ? at<uint32_t>(ws, L.gtoff) : nullptr;
-  // bucket path: the first partition level planned before the key pass when its digit comes from
-  // k1 alone (segment.h k_level1_plan), so the key pass writes the level-1 children itself
-  const bool planned = bucket && L.max_ent <= kEntHistMax && n_ent > 0 && b.k1 >= kRadixBits &&
-                       !(nol1 && nol1[0] == '1');
-  L1Plan l1{};
-  if (planned) {
-    // SCT_L1_BITS=1..8 (a test switch): every entity's first level on that many bits (8: the uniform
-    // cut of the rounds before 7) instead of the width its size asks for (bucket.h l1_width)
-    const char* l1b = getenv("SCT_L1_BITS");
-    const int forced = l1b ? atoi(l1b) : 0;
-    l1 = L1Plan{at<uint32_t>(ws, L.ent_hist), at<uint32_t>(ws, L.l1_toff), at<uint2>(ws, L.l1_tslot),
-                at<Pay>(ws, L.pay_b), forced >= 1 && forced <= kRadixBits ? forced : 0};
-  }
-  const uint8_t* mito = gene_is_mito;
-  // every buffer the step zeroes before its first kernel, in one launch
-  FillBatch fb;
-  if (cell && !mito) {
-    uint8_t* z = at<uint8_t>(ws, L.zero_mito);
-    fb.add(z, (size_t)plan->n_gene_ids);
-    mito = z;
-  }
-  fb.add(partials, sizeof(int64_t) * SCT_NP * (size_t)n_ent);
-  if (gene) {
-    fb.add(gcounts, sizeof(uint32_t) * (size_t)L.n_buckets);
-    fb.add(gene_partials, sizeof(int64_t) * SCT_NP * (size_t)plan->n_gene_ids);  // (written by gene_reduce only)
-  }
-
-  // 1. input order: runs, keys, additive metrics (+ gene-bucket counts per tile)
-  const dim3 tgrid((unsigned)cdiv(n, kKTile));  // key-pass blocks (tile offsets are per kTile)
-  const uint64_t* toff = at<uint64_t>(ws, L.tile_cnt);
-  // exact mean / variance lanes of the output rows ride along in the same launch
-  const bool streams = exact && out_i;
-  BucketCtl* ctl = bucket_ctl(ws, L);
-  fb.add(ctl, sizeof(BucketCtl));
-  // gene payload format: narrow (8 B) unless an operand does not fit (checked by the exact-stream
-  // pass; without it the wide format is used)
-  uint32_t* gwide = reinterpret_cast<uint32_t*>(at<uint64_t>(ws, L.scalars) + 16);
-  fb.add(gwide, sizeof(uint32_t), streams ? 0 : 1);
-  if (planned) level1_fills(L, ws, n, n_ent, l1, fb, may_plan);
-  rc = launch_fills(fb, s);
-  if (rc) return rc;
-  // Round 8: on the planned bucket path with exact floats the quality-stream lanes run as a kernel
-  // of their own (segment.h k_stream_lanes) on the side pool's second stream, and the key pass
-  // without them.  They fork here (the fills above zeroed the partial rows and gwide): beside the
-  // level-1 plan and its classification, which are latency-bound, and whatever is left beside the
-  // key pass.  (A fork after the key pass, beside the partition levels >= 2, measured no gain: the
-  // early big buckets fill that stretch)  SCT_STREAM_LANES=fused (a test
-  // switch; pre: this path, the default) keeps the one launch, and so does a call that finds another
-  // call's pair in use on the device (the pool would then open further streams, and a process has 4
-  // hardware queues).
-  SideStream side;
-  const char* no_side = getenv("SCT_NO_SIDE");
-  const bool use_side = bucket && planned && exact && !(no_side && no_side[0] == '1');
-  const char* lanes_sw = getenv("SCT_STREAM_LANES");
-  bool split = use_side && streams && n > 0 && !(lanes_sw && !strcmp(lanes_sw, "fused"));
-  if (split) {
-    HIPCHK(side.open(s));
-    split = side.alone;
-  }
-  if (split) {
-    hipStream_t sp = nullptr;
-    HIPCHK(side.pair_fork(s, &sp));
-    uint32_t* gw = gene ? gwide : nullptr;
-    if (cell) {
-      LAUNCH_N("stream_lanes", n, k_stream_lanes<true>, tgrid, dim3(kBlock), sp, rc2, n, toff, hbits, partials, gw);
-    } else {
-      LAUNCH_N("stream_lanes", n, k_stream_lanes<false>, tgrid, dim3(kBlock), sp, rc2, n, toff, hbits, partials, gw);
-    }
-    HIPCHK(side.pair_mark());
-  }
-  if (planned) {
-    rc = bucket_level1_plan(L, ws, kc, n, n_ent, b, ent_start, l1, s);
-    if (rc) return rc;
-    // level 1's counts, final after its classification: copied now, read by bucket_distinct while
-    // the key pass runs (no host wait between the key pass and level 2)
-    if (int rb = readback_start(bucket_ctl(ws, L), sizeof(BucketCtl), s)) return rb;
-  }
+int run_step(const StepCall& c, const StepSwitches& sw, bool allow_bucket) {
+  const Layout L = layout_for(c.plan);
+  if (!c.ws || c.ws_bytes < L.total) return fail(SCT_ENOMEM, "workspace too small (%zu < %zu)", c.ws_bytes, L.total);
+  Step S(c, sw, L, allow_bucket);
+  if (int rc = count_stage(S)) return rc;                                                     // 1
+  if (int rc = plan_key_bits(S.bucket, S.n_ent, &S.b, &S.used)) return rc;                    // 2
+  if (int rc = fills_stage(S)) return rc;                                                     // 3
+  if (int rc = fork_lanes(S)) return rc;                                                      // 4
+  if (S.planned)
+    if (int rc = bucket_level1_plan(S)) return rc;                                            // 5
   // Welford (the drop-in default): forked as soon as the entity starts exist -- after the level-1
   // plan when there is one (round 4: the head group's chains then start before the key pass),
   // else after the key pass
-  WelfordSide wf;
-  const bool wf_fork_early = planned && !exact && out_i;
-  if (wf_fork_early) {
-    rc = welford_stage(L, ws, cell, n, n_ent, rc2, ent_start, out_f, s, wf);
-    if (rc) return rc;
+  const bool welford = !S.exact && c.out_i;
+  if (welford && S.planned)
+    if (int rc = welford_stage(S)) return rc;                                                 // 6
+  if (int rc = key_pass(S)) return rc;                                                        // 7
+  if (welford && !S.planned)
+    if (int rc = welford_stage(S)) return rc;                                                 // 8
+  if (int rc = fork_side(S)) return rc;                                                       // 9
+  // 10. distinct counts (+ per-record distinct events for the gene view)
+  if (int rc = S.bucket ? bucket_distinct(S) : sorted_distinct(S)) {
+    if (rc != kRedoGlobalSort) return rc;
+    // a mapped ref id does not fit the bucket payload: redo on the global-sort path, which reuses the
+    // workspace, under the switches this pass read
+    HIPCHK(S.st.drain());
+    return run_step(c, sw, false);
   }
-
-  if (bucket) {
-    uint64_t* pay = at<uint64_t>(ws, L.pay_a);  // (the bucket path writes Pay records through `keys`)
-    rc = streams && !split
-             ? launch_build_keys<true, true>(cell, gene, tgrid, s, kc, rc2, mito, n, toff, b, pay, nullptr, hbits,
-                                             ent_start, partials, gcounts, L.n_buckets, &ctl->err, gwide, gtoff, l1)
-             : launch_build_keys<true, false>(cell, gene, tgrid, s, kc, rc2, mito, n, toff, b, pay, nullptr, hbits,
-                                              ent_start, partials, gcounts, L.n_buckets, &ctl->err, gwide, gtoff, l1);
-  } else {
-    rc = streams ? launch_build_keys<false, true>(cell, gene, tgrid, s, kc, rc2, mito, n, toff, b, B.ka, B.va, hbits,
-                                                  ent_start, partials, gcounts, L.n_buckets, &ctl->err, gwide, gtoff,
-                                                  l1)
-                 : launch_build_keys<false, false>(cell, gene, tgrid, s, kc, rc2, mito, n, toff, b, B.ka, B.va, hbits,
-                                                   ent_start, partials, gcounts, L.n_buckets, &ctl->err, gwide, gtoff,
-                                                   l1);
-    if (rc) return rc;
-    uint32_t err = 0;  // the bucket path reads the flag at its first level sync
-    if (int rb = readback(&err, &ctl->err, sizeof(err), s)) return rb;
-    if (err & 2) return fail(SCT_EINVAL, "a gene / cell / umi id lies outside its dictionary size");
-  }
-  if (rc) return rc;
-  if (!wf_fork_early && !exact && out_i) {
-    rc = welford_stage(L, ws, cell, n, n_ent, rc2, ent_start, out_f, s, wf);
-    if (rc) return rc;
-  }
-
-  // Round 6: a side stream forked after the key pass (planned bucket path, exact floats) runs the
-  // gene view's plan and the big buckets of levels 0-1 beside the partition levels >= 2 and the
-  // hash tiles, and the cell rows' finalize beside the gene view
-  hipEvent_t plan_done = nullptr;
-  uint32_t* gcur = gene ? at<uint32_t>(ws, L.gcursor) : nullptr;
-  int64_t* gwork = gene ? at<int64_t>(ws, L.gwork) : nullptr;
-  int64_t* n_gwork = at<int64_t>(ws, L.scalars) + 4;
-  if (use_side) {
-    HIPCHK(side.open(s));
-    if (gene) {
-      LAUNCH_SHM("gene_plan", k_gene_plan, dim3(1), dim3(kBlock), 2 * sizeof(uint32_t) * (size_t)(L.n_buckets + 1),
-                 side.use(), (const uint32_t*)gcounts, L.n_buckets, gcur, gwork, n_gwork);
-      HIPCHK(side.event(&plan_done));
-      HIPCHK(hipEventRecord(plan_done, side.s));
-    }
-  }
-
-  // 2-3. distinct counts (+ per-record distinct events for the gene view)
-  uint16_t* dflags = gene ? at<uint16_t>(ws, L.dflags) : nullptr;
-  if (bucket) {
-    rc = bucket_distinct(L, ws, n, n_ent, ent_start, mito, b, cell, gene, partials, dflags, planned, s, side);
-    if (rc == 1) {  // a mapped ref id does not fit the bucket payload: redo on the global-sort path
-      if (wf.s2) HIPCHK(hipStreamSynchronize(wf.s2));  // (its workspace is reused by the redo)
-      if (wf.s3) HIPCHK(hipStreamSynchronize(wf.s3));
-      if (side.is_open()) HIPCHK(hipStreamSynchronize(side.s));
-      if (side.is_open() && !side.pair_synced) HIPCHK(hipStreamSynchronize(side.s_pair));  // (the stream lanes)
-      return pipeline(plan, rec, gene_is_mito, ws, ws_bytes, out_i, out_f, capacity, n_rows, gene_partials, s,
-                      false);
-    }
-    if (rc) return rc;
-  } else {
-    int which = 0;
-    rc = radix_sort(B, n, used + b.h, &which, s);
-    if (rc) return rc;
-    const uint64_t* keys = which ? B.kb : B.ka;
-    const uint32_t* vals = which ? B.vb : B.va;
-    const dim3 rgrid((unsigned)cdiv(n, kReduceTile));
-    if (cell && gene) {
-      LAUNCH_N("reduce_sorted", n, (k_reduce_sorted<true, true>), rgrid, dim3(kBlock), s, keys, vals, n, rc2, mito, b,
-             partials, dflags);
-    } else if (cell) {
-      LAUNCH_N("reduce_sorted", n, (k_reduce_sorted<true, false>), rgrid, dim3(kBlock), s, keys, vals, n, rc2, mito, b,
-             partials, dflags);
-    } else {
-      LAUNCH_N("reduce_sorted", n, (k_reduce_sorted<false, false>), rgrid, dim3(kBlock), s, keys, vals, n, rc2, mito, b,
-             partials, dflags);
-    }
-  }
-
-  // the stream lanes (k_stream_lanes on the pair stream) are complete before the rows' finalize reads
-  // their slots, on whichever stream it runs (the side stream forks from the caller's below), and
-  // before k_gene_emit reads gwide
-  if (split) HIPCHK(side.pair_join(s));
-  if (out_i) {
-    const char* no_sfin = getenv("SCT_NO_SIDE_FIN");
-    const bool side_fin = side.is_open() && gene && !(no_sfin && no_sfin[0] == '1');
-    if (side_fin) HIPCHK(side.from_caller(s));
-    hipStream_t fs = side_fin ? side.use() : s;
-    LAUNCH("finalize", k_finalize, dim3((unsigned)cdiv(n_ent * kFinThreads, kBlock)), dim3(kBlock), fs, (const int64_t*)partials,
-           n_ent, cell ? SCT_MODE_CELL : SCT_MODE_GENE, exact ? 1 : 0, (const int64_t*)ent_start, out_i, out_f);
-    if (!exact) {  // launched on the side streams after the key pass (welford_stage): joined here
-      HIPCHK(hipEventRecord(wf.join, wf.s2));
-      HIPCHK(hipStreamWaitEvent(s, wf.join, 0));
-      HIPCHK(hipEventRecord(wf.join3, wf.s3));
-      HIPCHK(hipStreamWaitEvent(s, wf.join3, 0));
-    }
-  }
-  if (gene) {
-    // 4. gene view: bucket starts, payload emission (input order), bucket reduction
-    void* gpay = at<GenePayload>(ws, L.gpay);
-    if (plan_done) {
-      HIPCHK(hipStreamWaitEvent(s, plan_done, 0));
-    } else {
-      LAUNCH_SHM("gene_plan", k_gene_plan, dim3(1), dim3(kBlock), 2 * sizeof(uint32_t) * (size_t)(L.n_buckets + 1), s,
-                 (const uint32_t*)gcounts, L.n_buckets, gcur, gwork, n_gwork);
-    }
-    static_assert(kEmitTile == kKTile, "gene_emit tiles are the key pass's tiles (gtoff)");
-    const int staged = L.n_buckets <= kEmitStagedBuckets ? 1 : 0;
-    LAUNCH_SHM_N("gene_emit", n, k_gene_emit, dim3((unsigned)cdiv(n, kEmitTile)), dim3(kBlock),
-               (staged ? 3 : 2) * sizeof(uint32_t) * (size_t)L.n_buckets, s, rec->gene, rc2, (const uint16_t*)dflags,
-               n, (const uint32_t*)gcur, (const uint32_t*)gtoff, L.n_buckets, (const uint32_t*)gwide, staged, gpay);
-    LAUNCH_N("gene_reduce", n, k_gene_reduce, dim3((unsigned)L.max_gene_work), dim3(kBlock), s, (const void*)gpay,
-           (const int64_t*)gwork, (const int64_t*)n_gwork, plan->n_gene_ids, (const uint32_t*)gwide, gene_partials);
-  }
-  if (side.is_open()) HIPCHK(side.to_caller(s));
-  if (n_rows) *n_rows = n_ent;
+  // 11. the stream lanes are complete before the rows' finalize reads their slots, on whichever
+  // stream it runs, and before k_gene_emit reads gwide
+  if (S.split) HIPCHK(S.st.join(1, S.lanes_done));
+  if (int rc = finalize_stage(S)) return rc;                                                  // 12
+  if (int rc = gene_stage(S)) return rc;                                                      // 13
+  if (S.use_side) HIPCHK(S.st.join(0));                                                       // 14
+  if (c.n_rows) *c.n_rows = S.n_ent;
   return SCT_OK;
 }
+
+int pipeline(const StepCall& c) { return run_step(c, StepSwitches{}, true); }
 
 // ---- tag sort ----
 struct SortLayout {
@@ -1153,7 +995,7 @@ int sct_count_entities(const sct_plan_t* plan, const sct_records_t* rec, void* w
   const Layout L = layout_for(&p1);
   if (!workspace || workspace_bytes < count_bytes(L))
     return fail(SCT_ENOMEM, "workspace too small for counting (%zu < %zu)", workspace_bytes, count_bytes(L));
-  return count_runs(plan->mode == SCT_MODE_CELL ? rec->cell : rec->gene, rec->n, workspace, L, false, 0, n_entities,
+  return count_runs(plan->mode == SCT_MODE_CELL ? rec->cell : rec->gene, rec->n, workspace, L, CountOpts{}, n_entities,
                     nullptr, (hipStream_t)stream);
 }
 
@@ -1172,8 +1014,8 @@ int sct_compute_metrics(const sct_plan_t* plan, const sct_records_t* rec, const 
     *n_rows = 0;
     return SCT_OK;
   }
-  return pipeline(plan, rec, gene_is_mito, workspace, workspace_bytes, out_ints, out_floats, capacity, n_rows,
-                  nullptr, (hipStream_t)stream);
+  return pipeline(StepCall{plan, rec, gene_is_mito, workspace, workspace_bytes, out_ints, out_floats, capacity, n_rows,
+                           nullptr, (hipStream_t)stream});
 }
 
 int sct_gene_partials(const sct_plan_t* plan, const sct_records_t* rec, void* workspace, size_t workspace_bytes,
@@ -1189,7 +1031,7 @@ int sct_gene_partials(const sct_plan_t* plan, const sct_records_t* rec, void* wo
     HIPCHK(hipMemsetAsync(partials, 0, sizeof(int64_t) * SCT_NP * (size_t)plan->n_gene_ids, s));
     return SCT_OK;
   }
-  return pipeline(plan, rec, nullptr, workspace, workspace_bytes, nullptr, nullptr, 0, nullptr, partials, s);
+  return pipeline(StepCall{plan, rec, nullptr, workspace, workspace_bytes, nullptr, nullptr, 0, nullptr, partials, s});
 }
 
 int sct_cell_metrics_gene_partials(const sct_plan_t* plan, const sct_records_t* rec, const uint8_t* gene_is_mito,
@@ -1207,8 +1049,8 @@ int sct_cell_metrics_gene_partials(const sct_plan_t* plan, const sct_records_t* 
     HIPCHK(hipMemsetAsync(gene_partials, 0, sizeof(int64_t) * SCT_NP * (size_t)plan->n_gene_ids, s));
     return SCT_OK;
   }
-  return pipeline(plan, rec, gene_is_mito, workspace, workspace_bytes, out_ints, out_floats, capacity, n_rows,
-                  gene_partials, s);
+  return pipeline(StepCall{plan, rec, gene_is_mito, workspace, workspace_bytes, out_ints, out_floats, capacity, n_rows,
+                           gene_partials, s});
 }
 
 int sct_tag_sort_workspace_size(const sct_plan_t* plan, size_t* bytes) {
@@ -1275,15 +1117,13 @@ int sct_tag_sort(const sct_plan_t* plan, const sct_records_t* in, const int32_t*
   const dim3 grid((unsigned)cdiv(n, kBlock));
   // (CB, UB, GE[, query name]) by groups (tagsort.h, round 6): an LSD sort of (cell, top umi bits) only,
   // then every group sorted inside its own positions
-  const char* grp_env = getenv("SCT_TAG_GROUP_SORT");
-  if (order == SCT_ORDER_CELL_UMI_GENE && !(grp_env && grp_env[0] == '0')) {
+  if (order == SCT_ORDER_CELL_UMI_GENE && !env_is("SCT_TAG_GROUP_SORT", '0')) {
     GroupBits gb{};
     gb.c = f[0].bits, gb.u = f[1].bits, gb.g = f[2].bits, gb.t = tiebreak ? f[3].bits : 0;
     const int ub_min = gb.u + gb.g + gb.t - 52 > 0 ? gb.u + gb.g + gb.t - 52 : 0;  // W fits 52 bits
     const int passes = (gb.c + ub_min + kRadixBits - 1) / kRadixBits;
     if (ub_min <= gb.u && passes <= 4) {
-      const char* msd_env = getenv("SCT_TAG_GROUP_MSD");
-      const bool msd = gb.c + ub_min > kRadixBits && !(msd_env && msd_env[0] == '0');
+      const bool msd = gb.c + ub_min > kRadixBits && !env_is("SCT_TAG_GROUP_MSD", '0');
       // K1 is filled to the width its passes sort anyway (smaller groups for free): LSD, whole 8-bit
       // digits; MSD, the kMsdBits-bit top digit plus the fewest 8-bit segmented passes (<= 32 bits)
       int kw = kRadixBits * passes;
@@ -1732,21 +1572,17 @@ int sct_tagsort_metrics(const sct_plan_t* plan, const sct_records_t* rec, const 
                         hipMemcpyDeviceToDevice, s));
   if (n > 0) {
     const unsigned slot_blocks = (unsigned)(L.slots / kBlock);
-    if (cell) {
-      LAUNCH_N("ts_records", n, (k_ts_records<true>), dim3(rec_blocks), dim3(kBlock), s, *rec, n, first_drop,
-               third_is_mito, ent, row_start, ft, kt, xv, out_ints);
-    } else {
-      LAUNCH_N("ts_records", n, (k_ts_records<false>), dim3(rec_blocks), dim3(kBlock), s, *rec, n, first_drop,
-               third_is_mito, ent, row_start, ft, kt, xv, out_ints);
-    }
+#define SCT_TS_RECORDS(C)                                                                                     \
+  LAUNCH_N("ts_records", n, (k_ts_records<C>), dim3(rec_blocks), dim3(kBlock), s, *rec, n, first_drop, third_is_mito, \
+           ent, row_start, ft, kt, xv, out_ints)
+    SCT_VIEW2(cell, SCT_TS_RECORDS);
+#undef SCT_TS_RECORDS
     LAUNCH_N("ts_frag_slots", L.slots, k_ts_frag_slots, dim3(slot_blocks), dim3(kBlock), s, *rec, ent, ft, out_ints);
-    if (cell) {
-      LAUNCH_N("ts_k1_slots", L.slots, (k_ts_k1_slots<true>), dim3(slot_blocks), dim3(kBlock), s, *rec, third_is_mito,
-               ent, kt, out_ints);
-    } else {
-      LAUNCH_N("ts_k1_slots", L.slots, (k_ts_k1_slots<false>), dim3(slot_blocks), dim3(kBlock), s, *rec, third_is_mito,
-               ent, kt, out_ints);
-    }
+#define SCT_TS_K1(C)                                                                                              \
+  LAUNCH_N("ts_k1_slots", L.slots, (k_ts_k1_slots<C>), dim3(slot_blocks), dim3(kBlock), s, *rec, third_is_mito, ent, kt, \
+           out_ints)
+    SCT_VIEW2(cell, SCT_TS_K1);
+#undef SCT_TS_K1
     LAUNCH_N("ts_chains", n, k_ts_chains, dim3((unsigned)rows), dim3(kWave), s, (const uint4*)xv, n, rows,
              (const int32_t*)row_start, out_sums);
   }
