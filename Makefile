@@ -4,7 +4,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 HIPFLAGS ?= --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -Wall
 ENGINE := sctools_amd/libsctools_gpu.so
 SRC := sctools_amd/csrc/sct_engine.hip
-HDRS := $(wildcard sctools_amd/csrc/*.h) include/sctools_gpu.h
+HDRS := $(filter-out sctools_amd/csrc/gbam_%.h,$(wildcard sctools_amd/csrc/*.h)) include/sctools_gpu.h
 
 BAMDEC := sctools_amd/libsct_bam.so
 CSVFMT := sctools_amd/libsct_csv.so
@@ -26,7 +26,7 @@ $(SI4): $(SRC) $(HDRS)
 $(BAMDEC): sctools_amd/csrc/bamdec.cpp sctools_amd/csrc/bamsplit.cpp sctools_amd/csrc/bamtag.cpp sctools_amd/csrc/bamshards.cpp sctools_amd/csrc/bamwrite.h sctools_amd/csrc/bgzf.h include/sct_bam.h
 	g++ -O3 -std=c++17 -fopenmp -fPIC -shared -Wall -o $@ sctools_amd/csrc/bamdec.cpp sctools_amd/csrc/bamsplit.cpp sctools_amd/csrc/bamtag.cpp sctools_amd/csrc/bamshards.cpp -lz
 
-$(GBAM): sctools_amd/csrc/gbam.hip sctools_amd/csrc/inflate.h sctools_amd/csrc/bgzf.h include/sct_gbam.h include/sct_bam.h
+$(GBAM): sctools_amd/csrc/gbam.hip $(wildcard sctools_amd/csrc/gbam_*.h) sctools_amd/csrc/inflate.h sctools_amd/csrc/bgzf.h include/sct_gbam.h include/sct_bam.h
 	$(HIPCC) $(HIPFLAGS) -o $@ sctools_amd/csrc/gbam.hip -lz
 
 $(BARCODE): sctools_amd/csrc/barcode.hip sctools_amd/csrc/liberr.h include/sct_barcode.h

@@ -1,6 +1,6 @@
 """Device BAM decode timing (experiments): stages of gbam.decode on one BAM, best of --reps.
 
-python tools/gbam_time.py BAM [--reps 3] [--mode cell|gene|tagsort] [--tags CB UB GE]
+python tools/gbam_time.py BAM [--reps 3] [--mode cell|gene|tagsort|count] [--tags CB UB GE]
 (SCT_GBAM_LIB_PATH selects an experimental library)
 """
 import argparse
@@ -16,9 +16,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("bam")
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--mode", default="cell", choices=["cell", "gene", "tagsort"])
+    ap.add_argument("--mode", default="cell", choices=["cell", "gene", "tagsort", "count"])
     ap.add_argument("--tags", nargs=3, default=["CB", "UB", "GE"], metavar=("BARCODE", "UMI", "GENE"),
-                    help="the three tag names of --mode tagsort")
+                    help="the three tag names of --mode tagsort and --mode count")
     a = ap.parse_args()
     import torch
 
@@ -31,7 +31,7 @@ def main():
         tm = {}
         t0 = time.perf_counter()
         got = gbam.decode(a.bam, a.mode, dev, timings=tm, lazy=True,
-                          tags=tuple(a.tags) if a.mode == "tagsort" else None)
+                          tags=tuple(a.tags) if a.mode in ("tagsort", "count") else None)
         torch.cuda.synchronize()
         t = time.perf_counter() - t0
         if got is None:

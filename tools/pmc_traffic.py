@@ -21,14 +21,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # the device BAM decoder's and host decoders' sources are not part of the engine library the PMC
 # passes measure (libsctools_gpu.so: sct_engine.hip and the headers it includes)
-NOT_ENGINE = ("gbam.hip", "inflate.h", "bgzf.h")
+NOT_ENGINE = ("gbam.hip", "inflate.h", "bgzf.h")  # and the decoder's stage headers, gbam_*.h
 
 
 def source_hash(root=ROOT):
     d = os.path.join(root, "sctools_amd", "csrc")
     h = hashlib.sha256()
     for f in sorted(os.listdir(d)):
-        if f.endswith((".h", ".hip")) and f not in NOT_ENGINE:
+        if f.endswith((".h", ".hip")) and f not in NOT_ENGINE and not f.startswith("gbam_"):
             h.update(f.encode())
             h.update(open(os.path.join(d, f), "rb").read())
     return h.hexdigest()
